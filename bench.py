@@ -10,10 +10,12 @@ one window of halo rows resident, computes the owned SNPs (no hot-path exchange)
 gathered to rank 0 over RCCL every step.  `--weak` runs one chromosome per GPU instead.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the band correlation kernel (HIP events on the
-engine's stream, averaged over the timed steps), on SURVEY.md §8(d3)'s FLOP basis; `wall_clock_from_file_s`
-times the drop-in `_ldscore.calculate` from the .bed written to local disk; `cpu_baseline` times the C port of the reference's
-CPU path (oracle/, fp32 sdot per pair, OpenMP over window neighbours) on the first SNPs of the same
-chromosome (rank 0, N = 1 only).
+engine's stream, averaged over the timed steps), on SURVEY.md §8(d3)'s FLOP basis.  A plain run does only what that
+line's headline needs (set-up, warm-up, the timed steps).  `--full` adds the measurements that take runs of their own
+(rank 0, N = 1, C3): `fp32_path` and `oneshot_gpu_ms` (extra_records), `wall_clock_from_file_s`, which
+times the drop-in `_ldscore.calculate` from the .bed written to local disk, and `cpu_baseline`, which times the C port
+of the reference's CPU path (oracle/, fp32 sdot per pair, OpenMP over window neighbours) on the first SNPs of the same
+chromosome.  `--dump-outputs DIR` writes the score table of the last timed step as DIR/<name>.npy (float64).
 """
 import argparse
 import json
@@ -122,6 +124,26 @@ def table_digest(out) -> dict:
         if k in out:
             d[k + "_sum"] = float(np.nansum(np.asarray(out[k], dtype=np.float64)))
     return d
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs writes at most this much (float64 elements), headers apart
+
+
+def dump_outputs(directory: str, arrays: dict, prefix: str = "", budget: int = DUMP_BUDGET_BYTES) -> None:
+    """--dump-outputs: the arrays a caller of the timed path receives (one score table's columns, by name, all of one
+    length) as DIR/<prefix><name>.npy in float64 (the int32 window counts are exact in it).  A table above `budget`
+    bytes is sampled at SNP indices drawn once from a fixed seed, the same for every column (`sample_index.npy`)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    total = sum(a.size for a in arrays.values())
+    if 8 * total > budget:
+        n = min(a.shape[0] for a in arrays.values())
+        keep = max(1, min(n, (budget // 8) // (len(arrays) + 1)))
+        idx = np.sort(np.random.default_rng(20240607).choice(n, size=keep, replace=False))
+        np.save(os.path.join(directory, prefix + "sample_index.npy"), idx.astype(np.float64))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, prefix + k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_model() -> str:
@@ -303,7 +325,17 @@ def main():
     ap.add_argument("--path", choices=tuple(PATHS), default="f4",
                     help="correlation path: exact Gram on fp4 MFMAs (default), on int8 MFMAs, or fp32 "
                          "standardised values")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also take the measurements that need runs of their own (rank 0, "
+                         "N = 1, C3): the fp32 MFMA path and the one-shot load + run (--no-extra skips them), the wall "
+                         "clock from a PLINK file (--no-file) and the CPU baseline (--no-cpu); a plain run only sets "
+                         "up, warms up and times its steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the score table the last timed step returned (rank 0's gathered table; with --weak "
+                         "each rank's own, with c4 every chromosome's) as DIR/<name>.npy in float64, a fixed seeded "
+                         "sample of the SNPs when it would exceed 60 MB; the inputs are generated from fixed seeds, so "
+                         "two builds run with the same arguments can be compared output for output")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="collectives backend for N > 1 (gloo: rehearse several ranks on one GPU)")
@@ -321,7 +353,7 @@ def main():
                     help="one process on one GPU doing exactly what rank R of an N-GPU strong-scaling run does "
                          "(its owned range + halo resident, its share of the chromosome), without the gather")
     ap.add_argument("--no-file", action="store_true",
-                    help="skip the wall clock from a PLINK file (rank 0, N = 1: the synthetic .bed written to "
+                    help="--full: skip the wall clock from a PLINK file (rank 0, N = 1: the synthetic .bed written to "
                          "$TMPDIR, then _ldscore.calculate timed from the file)")
     ap.add_argument("--no-gather-overlap", action="store_true",
                     help="strong scaling over RCCL: gather each step's table before the next step starts (default: "
@@ -334,7 +366,7 @@ def main():
                     help="create the process group and run the sharded path (owned range, device table, collective "
                          "gather) even with one rank: the RCCL code of an N-GPU run rehearsed on one GPU")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the default line's extra records after the timed region (N = 1, C3): the fp32 MFMA path "
+                    help="--full: skip the extra records after the timed region (N = 1, C3): the fp32 MFMA path "
                          "(fp32_path) and the one-shot load + run GPU time (oneshot_gpu_ms)")
     ap.add_argument("--concurrent", type=int, default=3,
                     help="c4: chromosomes computed at once per GPU (host threads, one engine stream each)")
@@ -342,6 +374,8 @@ def main():
                     help="engine option (nldsc_engine_set_option, include/nldsc_ld.h), repeatable: a study of a "
                          "non-default schedule, e.g. --option debug_timing=1")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.engine_options = {k: int(v) for k, v in (o.split("=", 1) for o in args.option)}
 
     # --gpus N without a launcher: start the N ranks here (torch.distributed.run in a child process, before
@@ -450,12 +484,14 @@ def main():
         pos = pos_p
         out = _lib.alloc_result(M, pinned=True)[0]
     bed_host = None
-    want_file = rank == 0 and not use_dist and not args.no_file and args.workload == "c3"
-    if rank == 0 and not use_dist and (not args.no_cpu or want_file):
+    # --full (rank 0, N = 1): the measurements beside the headline, each a run of its own after the timed region
+    want_file = args.full and rank == 0 and not use_dist and not args.no_file and args.workload == "c3"
+    want_cpu = args.full and rank == 0 and not use_dist and not args.no_cpu
+    if want_cpu or want_file:
         bed_host = buf.cpu().numpy().tobytes()
     # (N = 1: the device image stays for the one-shot measurement after the timed region)
-    want_extra = (rank == 0 and not use_dist and not split and not args.no_extra and args.workload == "c3"
-                  and args.path == "f4")
+    want_extra = (args.full and rank == 0 and not use_dist and not split and not args.no_extra
+                  and args.workload == "c3" and args.path == "f4")
     img_dev = buf if want_extra else None
     del buf
     torch.cuda.empty_cache()
@@ -657,6 +693,8 @@ def main():
             "cpu_baseline": None,
             "table_digest": table_digest(out),
         }
+    if args.dump_outputs and out is not None:  # (a sharded run: rank 0 holds the gathered table)
+        dump_outputs(args.dump_outputs, out, prefix=f"rank{rank}_" if world > 1 and not split else "")
     if want_extra:
         res.update(extra_records(eng, img_dev, M, N, w, args, rsq, pos, flags, res,
                                  {k: np.array(v) for k, v in out.items()}))
@@ -664,7 +702,7 @@ def main():
     if want_file:
         log("[rank 0] wall clock from a PLINK file ...")
         res.update(file_wall_clock(bed_host, M, N, w, args.maf, args.std_thr, rsq, pos, flags))
-    if bed_host is not None and not args.no_cpu:
+    if want_cpu:
         log("[rank 0] timing the CPU baseline ...")
         res["cpu_baseline"] = cpu_baseline(bed_host, M, N, w, args.maf, args.std_thr, rsq, pos,
                                            target_s=args.cpu_seconds)
@@ -711,9 +749,11 @@ def whole_genome(args, world, rank, local, coll):
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(max_workers=max(1, args.concurrent))
 
+    last = {}  # chromosome unit -> the score table its latest run returned (--dump-outputs)
+
     def one(unit):
         u, e, pos = unit
-        e.run(args.window_cm, args.maf, args.std_thr, 1.0 / int(Mc[u]), pos, flags=flags)
+        last[u] = e.run(args.window_cm, args.maf, args.std_thr, 1.0 / int(Mc[u]), pos, flags=flags)
         return e.timings()["pairs"]
 
     def step():
@@ -736,6 +776,9 @@ def whole_genome(args, world, rank, local, coll):
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         dist.all_reduce(pr, op=dist.ReduceOp.SUM)
+    if args.dump_outputs:  # (each rank writes the chromosomes it computed)
+        for u, table in sorted(last.items()):
+            dump_outputs(args.dump_outputs, table, prefix=f"chr{u + 1:02d}_", budget=DUMP_BUDGET_BYTES // len(Mc))
     if rank == 0:
         t_max = float(el.item())
         print(json.dumps({

@@ -145,8 +145,8 @@ def test_bench_force_dist_rccl_one_rank():
 
 
 def test_bench_default_line_records_and_rehearsal():
-    """The default one-GPU bench line carries its extra records after the timed region (fp32_path: the fp32 MFMA
-    path on the same rows, its window counts equal to the default path's; oneshot_gpu_ms: load + run), and a
+    """The one-GPU bench line of a `--full` run carries its extra records after the timed region (fp32_path: the fp32
+    MFMA path on the same rows, its window counts equal to the default path's; oneshot_gpu_ms: load + run), and a
     rehearsal of one rank of 8 (`--rehearse 0/8`, a split run whose host result is the owned slice alone) skips them."""
     import json
     env = dict(os.environ)
@@ -158,14 +158,50 @@ def test_bench_default_line_records_and_rehearsal():
                            cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
         assert p.returncode == 0, p.stderr[-3000:]
         return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
-    d = bench()
+    d = bench("--full")
     f = d["fp32_path"]
     assert f["band_ms"] > 0 and 0 < f["frac"] < 1 and f["vs_default_path"]["l2_ws_equal"], f
     assert f["vs_default_path"]["l2d_ws_equal"] and f["vs_default_path"]["l2_max_abs_diff"] < 1e-3, f
     o = d["oneshot_gpu_ms"]
     assert o["load"] > 0 and o["run"] > 0 and abs(o["total"] - o["load"] - o["run"]) < 0.01, o
-    r = bench("--rehearse", "0/8")
+    r = bench("--full", "--rehearse", "0/8")
     assert "fp32_path" not in r and "oneshot_gpu_ms" not in r and r["value"] > 0, r
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_table(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times its steps and nothing else (no fp32_path, oneshot_gpu_ms,
+    wall clock from a file or CPU baseline: those are `--full`'s), and `--dump-outputs DIR` writes the score table the
+    last timed step returned: float64 columns equal, bit for bit, to an engine run over the same seeded chromosome."""
+    import json
+    from nldsc_amd import _lib, synth
+    from nldsc_amd.distributed import RESULT_KEYS
+    from nldsc_amd.engine import Engine
+    M, N = 6000, 20000
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--n-snp", str(M), "--n-org", str(N), "--length-cm", "21", "--dump-outputs",
+                        str(tmp_path / "dump")], cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "SNP-pairs/s" and d["higher_is_better"] is True, d
+    assert d["dtype"] == "fp4" and d["ms_per_step"] > 0, d
+    pairs = d["config"]["pairs_per_step_per_gpu"]  # value = pairs of the timed steps over their wall time
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - pairs) <= 1e-9 * pairs, d
+    for k in ("fp32_path", "oneshot_gpu_ms", "wall_clock_from_file_s", "wall_clock_from_file"):
+        assert k not in d, k
+    assert d["cpu_baseline"] is None and "timing the CPU baseline" not in p.stderr, d["cpu_baseline"]
+    assert sorted(os.listdir(tmp_path / "dump")) == sorted(k + ".npy" for k in RESULT_KEYS)
+    buf, pos = synth.device_bed(M, N, seed=7, length_cm=21.0, missing=0.01)  # bench.py's image (rank 0)
+    with Engine(0) as e:
+        e.load_bed_device(buf.data_ptr(), buf.numel(), M, N)
+        exp = e.run(1.0, 1e-4, 1e-5, 1.0 / M, pos, flags=_lib.FLAG_EXACT_F4)
+    for k in RESULT_KEYS:
+        got = np.load(tmp_path / "dump" / (k + ".npy"))
+        assert got.dtype == np.float64 and got.shape == (M,), (k, got.dtype, got.shape)
+        assert np.array_equal(got, np.asarray(exp[k], dtype=np.float64), equal_nan=True), k
+    assert np.isfinite(np.load(tmp_path / "dump" / "l2.npy")).sum() > M // 2
 
 
 SPLIT_SCRIPT = r'''

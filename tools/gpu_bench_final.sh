@@ -1,5 +1,5 @@
 #!/bin/bash
-# round end, after the PMC summaries of the current kernels are committed under profiles/: the default bench line
+# round end, after the PMC summaries of the current kernels are committed under profiles/: the `--full` bench line
 # (C3, file wall clock + CPU baseline), its rocprofv3 kernel statistics, and the C2 / C5-slice bench lines, each of
 # which reads its traffic from those summaries.   gpurun --timeout 1200 -- bash tools/gpu_bench_final.sh <tag>
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round checkpoint on the GPU box : GPU parity tests, smoke, the default bench (C3, file wall clock + CPU
+# Round checkpoint on the GPU box : GPU parity tests, smoke, the `--full` bench (C3, file wall clock + CPU
 # baseline), rocprofv3 kernel statistics of the same bench, PMC passes (HBM traffic, MFMA busy, clock, L2) of the
 # current kernels for C3, C2 and the C5 slice, their bench lines, a per-rank rehearsal of 8-GPU strong scaling and a
 # 2-rank gloo run of `bench.py --gpus 2` (the bench starting its own ranks).  Every step has its own time limit and
@@ -25,7 +25,7 @@ fi
 PH=${3:-all}
 if [ "$PH" = all ] || [ "$PH" = bench ]; then
 step bench
-timeout -k 10 400 python bench.py > $O/bench_c3.json 2> $O/bench_c3.err || { echo bench failed; tail $O/bench_c3.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err || { echo bench failed; tail $O/bench_c3.err; exit 1; }
 tail -c 400 $O/bench_c3.json
 step rocprof stats
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o k --output-format csv -- python3 bench.py --no-cpu --no-file --steps 5 > $O/prof_bench.json 2> $O/prof.err \
