@@ -148,6 +148,85 @@ void order_items_tiled(std::vector<PlanItem>& items, int nblk, int R, int C, std
     items.swap(scratch);
 }
 
+// K-split (f4, unsegmented rows) when the items fill the wave slots (2 per SIMD) in few, partly empty
+// rounds — a rank's shard of one chromosome — and splitting the K loop in P pieces fills them better
+// Model: a round of items takes ~0.67 us per K chunk (C3: 2 466 chunks, 1.65 ms per round, 12.7 rounds in
+// 20.9 ms); the split adds ~64 KiB of partial-tile traffic per piece at ~3 TB/s effective (measured: a 1/8
+// shard of C3, 3 300 items, band 3.35 -> 3.01 ms; a 1/2 shard, 13 000 items, P = 5 made it 7.5 % slower).
+int choose_ksplit(int n_items, int n_it, int n_cu, bool enabled) {
+    int ksplit = 1;
+    if (enabled && n_items > 0 && n_it <= F4_SEG_CHUNKS) {
+        const double slots = 8.0 * (double)n_cu, t_round = 0.67e-6 * n_it;
+        auto cost = [&](int P) {
+            return std::ceil((double)n_items * P / slots) / P * t_round +
+                   (P > 1 ? n_items * P * 65536.0 / 3e12 : 0.0);
+        };
+        double best = cost(1);
+        for (int P = 2; P <= 8 && 2 * P <= n_it; ++P)
+            if (cost(P) < 0.97 * best && (size_t)n_items * P * 32768 <= ((size_t)3 << 30)) {
+                best = cost(P);
+                ksplit = P;
+            }
+    }
+    return ksplit;
+}
+
+// single-block fp4 items in launches of one round of the wave slots (2 per SIMD): long unsegmented rows, at least
+// BAND_ROUND_MIN rounds of items
+static bool round_launches(int n_items, int n_it, int n_cu, bool use_f4, bool band_rounds) {
+    return band_rounds && use_f4 && n_it >= 1024 && n_it <= F4_SEG_CHUNKS && n_items >= BAND_ROUND_MIN * 8 * n_cu;
+}
+
+BandChoice choose_band(int n_items, int n_it, int n_cu, bool use_f4, bool ksplit_enabled, bool band_rounds,
+                       bool t2_cand) {
+    int ksplit = choose_ksplit(n_items, n_it, n_cu, ksplit_enabled);
+    // long rows: bands of at least BAND_ROUND_MIN rounds of wave slots go in round launches (the last, partial round
+    // K-split), not K-split whole — a 1/8 shard of C3 (1.6 rounds) band 2.70-2.76 -> 2.61-2.64 ms, a 1/4 shard
+    // (3.2 rounds) 5.21-5.26 -> 4.87-4.89 ms (profiles/r03_ab_round_min.txt; was from 4 rounds on)
+    // — in the single-block kernel, as the K-split it replaces: a shard's few super-items leave most CUs of the
+    // 4 x 4 kernel idle (a missing-free 1/8 shard of C3: 2.88 ms with it, 1.93-1.99 K-split whole)
+    bool rounds_forced = false;
+    if (round_launches(n_items, n_it, n_cu, use_f4, band_rounds)) {
+        rounds_forced = ksplit > 1;
+        ksplit = 1;
+    }
+    return {ksplit, t2_cand && ksplit == 1 && n_items > 0 && !rounds_forced};
+}
+
+// Unsegmented single-block fp4 items go in launches of one round of the wave slots each (2 per SIMD): the items
+// of a launch start together and, all of equal length, stay at nearby K offsets, so the waves on one XCD that
+// share a strip (the plan's 16 x 16 tiles) read it from that XCD's L2.  In one launch of all items the waves
+// drift apart and most strip bytes come from beyond L2 again (C3: 68 -> 14 GB per band, the clock 1.90 -> 2.02
+// GHz; band -2 to -4 % after the launch tails).  From one round of items on (BAND_ROUND_MIN), only for long rows: the
+// waves of a round also reach their epilogues together, which then no longer overlap another wave's products —
+// at N = 50 000 (strips of 0.4 MB, L2-resident anyway; epilogue ~1/3 of an item) round launches made the band
+// 2.8 -> 5.1 ms.  The last, partial round leaves wave slots idle for a whole item length (C3: 1 458 items in
+// 2 048 slots); those items are K-split instead when the cost model finds it cheaper (C3: P = 4, 3 rounds of 1/4
+// of an item).
+// rare-variant items of the single-block fp4 kernel run their K loops in the main launch (Gram tiles kept), their
+// epilogues after the replay (launch_band_f4 rep): unsegmented rows, no K-split of the whole band (whose
+// partial kernel already runs every item)
+SingleShape shape_single(int n_single, int n_it, int n_cu, bool use_f4, int ksplit, bool band_rounds, bool nc2,
+                         bool ksplit_ok, bool defer_wanted, size_t rep_gram_max_slots) {
+    SingleShape s;
+    s.round_items = ksplit == 1 && round_launches(n_single, n_it, n_cu, use_f4, band_rounds) ? 8 * n_cu : 0;
+    const int tail = s.round_items > 0 ? n_single % s.round_items : 0;
+    s.tail_p = tail > 0 ? choose_ksplit(tail, n_it, n_cu, use_f4 && !nc2 && ksplit_ok) : 1;
+    s.n_full = s.tail_p > 1 ? n_single - tail : n_single;
+    // slots for every block pair of the main launch (an upper bound: which items hold a replayed SNP is known on
+    // the device only); past rep_gram_max_slots (32 KiB each) the KC launch after the replay runs those items
+    // instead (a wide band of data with missing calls, where nearly every item stays in this kernel: ADVICE r03)
+    s.defer = defer_wanted && use_f4 && ksplit == 1 && n_it <= F4_SEG_CHUNKS &&
+              (size_t)s.n_full * (nc2 ? 2 : 1) <= rep_gram_max_slots;
+    return s;
+}
+
+int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it) {
+    if (use_t2) return t2_mode == 3 ? NLDSC_BAND_F4_QUAD : t2_mode == 1 ? NLDSC_BAND_F4_ROUTED : NLDSC_BAND_F4_2X2;
+    if (path != 2) return path != 0 ? NLDSC_BAND_I8 : NLDSC_BAND_F32;
+    return ksplit > 1 ? NLDSC_BAND_F4_KSPLIT : n_it > F4_SEG_CHUNKS ? NLDSC_BAND_F4_SEG : NLDSC_BAND_F4;
+}
+
 }  // namespace nldsc
 
 extern "C" {

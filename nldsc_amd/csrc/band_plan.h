@@ -1,6 +1,7 @@
 // band_plan.h — host-side window replay (ChunkwiseReader, stream.h:131-155,182-197) and the band kernel's
 // work-item schedule; host-only C++ (no HIP), shared by ld_engine.cpp and the sanitizer build.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -19,5 +20,30 @@ bool positions_nonneg_sorted(const double* pos, int M);
 void plan_items(const double* pos, const uint8_t* flags, int M, double w, const int* L, const int* R, int own_begin,
                 int own_end, int max_nc, std::vector<PlanItem>& out);
 void order_items_tiled(std::vector<PlanItem>& items, int nblk, int R, int C, std::vector<PlanItem>& scratch);
+
+// ---- launch shaping: how a run's band items go into kernel launches (pure arithmetic; ld_engine.cpp enqueue_band
+// and the schedule phases act on it, tests/native/plan_tsv_check.cpp pins it) ----
+
+// K-loop chunks (128 samples each) per fp32 accumulation segment of the fp4 path: rows longer than this
+// (N > 2^19) run the segmented kernel, which folds the fp32 Gram into int32 after every segment
+constexpr int F4_SEG_CHUNKS = 4096;
+// round launches from this many rounds of single-block items on
+constexpr int BAND_ROUND_MIN = 1;
+
+// K-split pieces P (1: none) for n_items single-block fp4 items of n_it chunks on n_cu CUs; enabled: fp4, no
+// column-block pair items, option "ksplit"
+int choose_ksplit(int n_items, int n_it, int n_cu, bool enabled);
+// the whole band: its K-split (overridden to 1 where the band goes in round launches) and whether the super-item
+// kernels run (t2_cand: the run qualifies for them)
+struct BandChoice { int ksplit; bool use_t2; };
+BandChoice choose_band(int n_items, int n_it, int n_cu, bool use_f4, bool ksplit_enabled, bool band_rounds,
+                       bool t2_cand);
+// the single-block launches of n_single items: items [0, n_full) in launches of round_items (0: one launch), the
+// rest K-split in tail_p pieces (1: no tail launch, n_full = n_single); defer: rare-variant epilogues after the replay
+struct SingleShape { int round_items, tail_p, n_full; bool defer; };
+SingleShape shape_single(int n_single, int n_it, int n_cu, bool use_f4, int ksplit, bool band_rounds, bool nc2,
+                         bool ksplit_ok, bool defer_wanted, size_t rep_gram_max_slots);
+// NLDSC_BAND_* (nldsc_ld.h) of a run; path: 0 fp32, 1 int8, 2 fp4; t2_mode: option "t2"
+int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it);
 
 }  // namespace nldsc

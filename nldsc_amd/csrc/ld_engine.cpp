@@ -77,10 +77,15 @@ int set_err(char* err, size_t errlen, int code, const char* fmt, ...) {
                            __FILE__, __LINE__, #expr);                                                \
     } while (0)
 
+// device buffer, freed with its owner (an engine's: on the engine's device, ~nldsc_engine)
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t want) {
         if (want <= n && p) return hipSuccess;
         if (p) (void)hipFree(p);
@@ -299,15 +304,17 @@ struct nldsc_engine {
     DevBuf<int4> rep_items;
     DevBuf<int> rep_count;
     bool defer_rep = true;
-    // a split run between its two calls (nldsc_engine_run_device_split / _finish)
-    bool split_pending = false;
-    int32_t split_M = 0, split_N = 0, split_row_bytes = 0, split_width = 0;
-    std::pair<int32_t, int32_t> split_own{0, 0};
-    bool split_dom = true;
-    double* split_table = nullptr;
-    double split_ms1 = 0.0;  // the first call's host time
+    // the device table of a run (finish_table's input), kept for a split run between its two calls
+    // (nldsc_engine_run_device_split / _finish: `pending`)
+    struct SplitState {
+        bool pending = false;
+        int32_t M = 0, N = 0, row_bytes = 0, width = 0;
+        int32_t own_lo = 0, own_hi = 0;
+        bool dom = true;
+        double* table = nullptr;
+        double ms1 = 0.0;  // the first call's host time
+    } split;
     bool ksplit_ok = true;    // option "ksplit" 0 disables the K-split
-    static constexpr int round_min = 1;  // round launches from this many rounds of single-block items on
     // deferred rare-variant Gram tiles: at most this many block-pair slots (32 KiB each: 2 GiB)
     size_t rep_gram_max_slots = (size_t)1 << 16;
     int last_ksplit = 1;
@@ -367,20 +374,12 @@ struct nldsc_engine {
                            // (int8 from N = 2^27)
     int n_cu = 256;
 
+    // (the DevBuf members free themselves after this body: on `device`, set here)
     ~nldsc_engine() {
         (void)hipSetDevice(device);
-        bed.release(); stage_dev.release(); lastb.release(); flip.release(); row_miss.release(); miss_flags.release();
-        lcounts.release();
-        counts.release(); Lw.release(); Rw.release(); Aw.release(); ws_acc.release();
-        res.release(); lut.release(); cst.release(); sflags.release(); pos.release();
-        l2_acc.release(); l2d_acc.release(); items.release(); gram.release();
-        rep_gram.release(); rep_items.release(); rep_count.release();
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
         for (auto& e : ev_dbg) if (e) (void)hipEventDestroy(e);
         if (ev_plan) (void)hipEventDestroy(ev_plan);
-        plan_counts.release(); plan_meta.release(); plan_rows.release();
-        plan_counts2.release(); plan_rows2.release(); items2.release(); blk_miss.release(); sums.release();
-        cparts.release();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         if (ev_issued) (void)hipEventDestroy(ev_issued);
         if (stream) (void)hipStreamDestroy(stream);
@@ -389,7 +388,6 @@ struct nldsc_engine {
         if (ev_stats) (void)hipEventDestroy(ev_stats);
         if (ev_replay) (void)hipEventDestroy(ev_replay);
         if (ev_route) (void)hipEventDestroy(ev_route);
-        items_u.release(); compact_tmp.release();
     }
 };
 
@@ -771,18 +769,88 @@ int nldsc_engine_load_bed_file(nldsc_engine* e, const char* path, int32_t n_snp,
 
 namespace {
 
-// The hot path of one run.  Results go to the host arrays of `r`, or (table_dev != nullptr) stay in device memory
-// as the owned slice of the score table (nldsc_engine_run_device).
-// Split runs (nldsc_engine_run_device_split, export_n != nullptr): only the pairs whose lower SNP is owned are computed,
-// the per-SNP sums of every SNP of the slice accumulate, the right halo's [own_end, M) go out to export_dev and the run
-// stops before finalize; nldsc_engine_run_device_finish adds the left neighbour's export and finishes.
-int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end, nldsc_ld_result* r,
-             double* table_dev, int32_t width, char* err, size_t errlen, long long* export_dev = nullptr,
-             int32_t export_cap = 0, int32_t* export_n = nullptr) {
-    const bool split = export_n != nullptr;
+using Clock = std::chrono::steady_clock;
+double ms_between(Clock::time_point a, Clock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+// What a run's parameters alone decide (with the engine's default path): sizes of the resident image and the variant
+// of the kernels.
+struct RunShape {
+    int M, N, nb, row_bytes, pitch_words, n_it, nblk, Mpad;
+    uint32_t tail_keep;  // last .bed byte: the bit pairs that are individuals
+    bool dom, strict;
+    int order;  // bit of row_miss: the individual slots of this run's sample order
+    int path;   // 0 fp32, 1 exact int8, 2 exact fp4
+    bool use_i8, use_f4;
+    int max_nc;
+    bool replay, split;
+    int own_begin, own_end, flush_hi;
+};
+
+RunShape run_shape(const nldsc_engine* e, const nldsc_ld_params* p, int own_begin, int own_end, bool split) {
+    const int M = p->n_snp, N = p->n_org, row_bytes = row_pitch(N), nblk = (M + BLK - 1) / BLK;
+    const bool strict = (p->flags & NLDSC_FLAG_STRICT_PLINK_ORDER) != 0;
+    // last .bed byte: bit pairs that are individuals for the reference (high pairs first,
+    // stream.h:55-66) or for PLINK (low pairs first) — the rest are recoded as missing (-> 0)
+    const int rem = N % 4;
+    uint32_t tail_keep = 0xFFu;
+    if (rem) tail_keep = strict ? (uint32_t)((1u << (2 * rem)) - 1u) : (uint32_t)(0xFFu << (8 - 2 * rem)) & 0xFFu;
+    int path = (p->flags & NLDSC_FLAG_EXACT_F4) ? 2 : (p->flags & NLDSC_FLAG_EXACT_I8) ? 1
+             : (p->flags & NLDSC_FLAG_FP32) ? 0 : e->band_mode;
+    // fp4 Gram entries are <= 16N: the segmented fp4 kernel keeps them exact in int32 up to N < 2^27
+    if (path == 2 && N >= (1 << 27)) path = 1;
+    RunShape s = {};
+    s.M = M, s.N = N, s.nb = N / 4 + (N % 4 > 0), s.row_bytes = row_bytes, s.pitch_words = row_bytes / 4;
+    s.n_it = row_bytes / CHUNK_BYTES, s.nblk = nblk, s.Mpad = nblk * BLK, s.tail_keep = tail_keep;
+    s.dom = !(p->flags & NLDSC_FLAG_ADDITIVE_ONLY), s.strict = strict, s.order = strict ? 1 : 0;
+    s.path = path, s.use_i8 = path != 0, s.use_f4 = path == 2;
+    // rows longer than one fp32-exact segment: the segmented kernel (single blocks, register strips)
+    // fp32 items pair a row block with up to 2 column blocks (2 waves / SIMD); the exact paths take one
+    s.max_nc = s.use_i8 ? 1 : 2;
+    // rare variants: the reference's fp32 residual replayed (its sums assume N < 2^23)
+    s.replay = N < (1 << 23) && !(p->flags & NLDSC_FLAG_EXACT_RARE);
+    // per-SNP sums accumulate for the owned SNPs, or (split runs) for every SNP from own_begin on (the right halo's to
+    // be exported)
+    s.split = split, s.own_begin = own_begin, s.own_end = own_end, s.flush_hi = split ? M : own_end;
+    return s;
+}
+
+// How the band is scheduled: what the positions and the engine's options decide on top of the shape.
+struct PlanMode {
+    bool sorted, gpu_plan, fused, t2_cand, nc2, routed, quad;
+    int route_shift;  // super-items of 2^route_shift blocks a side
+};
+
+PlanMode plan_mode(const nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s) {
+    PlanMode m;
+    // band schedule: on the GPU when every position is >= 0 and sorted (the kernels run ahead of the
+    // count and the host only waits for two counters), else the host replay of the reference's pointers
+    const bool nonneg_sorted = nldsc::positions_nonneg_sorted(p->positions, s.M);
+    m.sorted = nonneg_sorted || nldsc::positions_sorted(p->positions, s.M);
+    m.gpu_plan = e->gpu_plan && nonneg_sorted && s.max_nc == 1;
+    m.fused = m.gpu_plan && e->plan_fused && s.M <= nldsc::PLAN_SMALL_N;
+    // the 2 x 2 block-pair workgroups: fp4, unsegmented rows, GPU plan, and no K-split (nldsc::choose_band); with
+    // super-item routing (t2 modes 1 and 3) only when a missing-free block exists in this run's sample order (routing
+    // takes none otherwise: C3 / C2 synthetic data, 1 % missing — the super plan, the compaction and two empty quad
+    // launches cost ~50 us per run)
+    m.t2_cand = e->t2_mode > 0 && m.gpu_plan && s.use_f4 && s.n_it <= nldsc::F4_SEG_CHUNKS && s.n_it >= 2 &&
+                (e->t2_mode == 2 || e->free_blocks[s.order] > 0);
+    // additive-only fp4 items of two column blocks (GPU plan, unsegmented rows; no K-split: its partial kernel takes
+    // single block pairs)
+    m.nc2 = e->f4_nc2 && m.gpu_plan && s.use_f4 && !s.dom && s.n_it <= nldsc::F4_SEG_CHUNKS;
+    m.routed = e->t2_mode == 1 || e->t2_mode == 3;
+    m.quad = e->t2_mode == 3;
+    m.route_shift = m.quad ? 2 : 1;
+    return m;
+}
+
+int check_run_args(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end, nldsc_ld_result* r,
+                   double* table_dev, int32_t width, bool split, long long* export_dev, int32_t export_cap, char* err,
+                   size_t errlen) {
     if (!e || !p || (!r && !table_dev)) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
     // any run overwrites the accumulators a pending split run left for run_device_finish
-    e->split_pending = false;
+    e->split.pending = false;
     if (!e->bed.p) return set_err(err, errlen, NLDSC_E_ARG, "no BED image loaded");
     if (p->n_snp != e->n_snp || p->n_org != e->n_org)
         return set_err(err, errlen, NLDSC_E_ARG, "params (%d SNPs x %d) do not match the loaded BED (%d x %d)",
@@ -790,7 +858,7 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     if (!p->positions) return set_err(err, errlen, NLDSC_E_ARG, "positions is NULL");
     if (!table_dev && (!r->l2 || !r->l2d || !r->maf || !r->residuals_std || !r->l2_ws || !r->l2d_ws || !r->l2d_wse))
         return set_err(err, errlen, NLDSC_E_ARG, "a result array is NULL");
-    const int M = p->n_snp, N = p->n_org;
+    const int M = p->n_snp;
     if (own_begin < 0 || own_end > M || own_begin > own_end)
         return set_err(err, errlen, NLDSC_E_ARG, "owned range [%d, %d) outside [0, %d)", own_begin, own_end, M);
     if (table_dev && (width <= 0 || width < own_end - own_begin))
@@ -802,186 +870,126 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     if (split && export_cap < p->n_snp - own_end)
         return set_err(err, errlen, NLDSC_E_ARG, "export capacity %d below the %d halo SNPs", export_cap,
                        p->n_snp - own_end);
-    if (own_begin == own_end) {  // nothing owned: no kernel runs and no output is written (an empty GPU plan
-        // would leave the left pointers unfilled); a device table is all NaN
-        for (int k = 0; k < 6; ++k) e->ms[k] = 0.0;
-        e->pairs = e->flop_alg = e->ops_alg_i8 = e->flop_issued = 0.0;
-        e->n_band_items = 0;
-        e->last_ksplit = 1;
-        e->last_tail_ksplit = 1;
-        e->last_round_items = 0;
-        e->last_direct = -1;
-        e->last_band_kernel = NLDSC_BAND_F4;
-        if (table_dev) {
-            HIPCHK(hipSetDevice(e->device));
-            HIPCHK(e->sums.ensure(3));
-            HIPCHK(hipMemsetAsync(e->sums.p, 0, 3 * sizeof(unsigned long long), e->stream));
-            HIPCHK(nldsc::launch_pack_table(e->l2.p, e->l2d.p, e->maf.p, e->rstd.p, e->ws3.p, M, own_begin, own_end,
-                                            width, table_dev, e->sums.p, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-        }
-        return NLDSC_OK;
+    return NLDSC_OK;
+}
+
+// nothing owned: no kernel runs and no output is written (an empty GPU plan would leave the left pointers unfilled); a
+// device table is all NaN
+int run_nothing_owned(nldsc_engine* e, int M, int own, double* table_dev, int32_t width, char* err, size_t errlen) {
+    for (int k = 0; k < 6; ++k) e->ms[k] = 0.0;
+    e->pairs = e->flop_alg = e->ops_alg_i8 = e->flop_issued = 0.0;
+    e->n_band_items = 0;
+    e->last_ksplit = e->last_tail_ksplit = 1;
+    e->last_round_items = 0;
+    e->last_direct = -1;
+    e->last_band_kernel = NLDSC_BAND_F4;
+    if (table_dev) {
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(e->sums.ensure(3));
+        HIPCHK(hipMemsetAsync(e->sums.p, 0, 3 * sizeof(unsigned long long), e->stream));
+        HIPCHK(nldsc::launch_pack_table(e->l2.p, e->l2d.p, e->maf.p, e->rstd.p, e->ws3.p, M, own, own, width,
+                                        table_dev, e->sums.p, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
     }
-    HIPCHK(hipSetDevice(e->device));
-    // Host-result runs (nldsc_engine_run): where the owned slice lands.  `out_h` are host pointers (DMA targets),
-    // `out_d` their device-mapped views (finalize_out_kernel writes them over the host link, no DMA after the band):
-    // the caller's arrays themselves when they lie in nldsc_host_alloc buffers (`direct`), else the engine's pinned
-    // landing buffer h_res, copied out by the host.  h_res also takes finalize's per-workgroup pair-count sums.
-    const bool host_out = table_dev == nullptr;
-    const int n_own = own_end - own_begin;
-    const size_t b8 = sizeof(double) * (size_t)n_own, b4 = sizeof(int32_t) * (size_t)n_own;
-    struct Out {
+    return NLDSC_OK;
+}
+
+// Host-result runs (nldsc_engine_run): where the owned slice lands.  `h` are host pointers (DMA targets), `d` their
+// device-mapped views (finalize_out_kernel writes them over the host link, no DMA after the band): the caller's arrays
+// themselves when they lie in nldsc_host_alloc buffers (`direct`), else the engine's pinned landing buffer h_res,
+// copied out by the host.  h_res also takes finalize's per-workgroup pair-count sums.
+struct HostOut {
+    struct Cols {
         double *l2, *l2d, *maf, *rstd;
         int32_t *wsa, *wsd, *wsde;
-    } out_h = {}, out_d = {};
-    bool direct = false;
-    unsigned long long* wsum_h = nullptr;
-    unsigned long long* wsum_d = nullptr;
-    const int n_wsum = nldsc::finalize_out_blocks(n_own);
-    e->last_direct = -1;
-    if (host_out) {
-        const size_t o = (size_t)own_begin, wsum_off = (4 * b8 + 3 * b4 + 7) / 8 * 8;
-        HIPCHK(e->h_res.ensure(wsum_off + 2 * sizeof(unsigned long long) * (size_t)n_wsum));
-        uint8_t* dres = nullptr;
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dres), e->h_res.p, 0));
-        wsum_h = reinterpret_cast<unsigned long long*>(e->h_res.p + wsum_off);
-        wsum_d = reinterpret_cast<unsigned long long*>(dres + wsum_off);
-        const Out callers = {r->l2 + o, r->l2d + o, r->maf + o, r->residuals_std + o, r->l2_ws + o, r->l2d_ws + o,
-                             r->l2d_wse + o};
-        Out reg = {};
-        reg.l2 = static_cast<double*>(registered_device_ptr(callers.l2, b8));
-        reg.l2d = static_cast<double*>(registered_device_ptr(callers.l2d, b8));
-        reg.maf = static_cast<double*>(registered_device_ptr(callers.maf, b8));
-        reg.rstd = static_cast<double*>(registered_device_ptr(callers.rstd, b8));
-        reg.wsa = static_cast<int32_t*>(registered_device_ptr(callers.wsa, b4));
-        reg.wsd = static_cast<int32_t*>(registered_device_ptr(callers.wsd, b4));
-        reg.wsde = static_cast<int32_t*>(registered_device_ptr(callers.wsde, b4));
-        direct = reg.l2 && reg.l2d && reg.maf && reg.rstd && reg.wsa && reg.wsd && reg.wsde;
-        e->last_direct = direct ? 1 : 0;
-        if (direct) {
-            out_h = callers;
-            out_d = reg;
-        } else {
-            auto at = [&](uint8_t* base, size_t off) { return base + off; };
-            out_h = {reinterpret_cast<double*>(at(e->h_res.p, 0)), reinterpret_cast<double*>(at(e->h_res.p, b8)),
-                     reinterpret_cast<double*>(at(e->h_res.p, 2 * b8)), reinterpret_cast<double*>(at(e->h_res.p, 3 * b8)),
-                     reinterpret_cast<int32_t*>(at(e->h_res.p, 4 * b8)),
-                     reinterpret_cast<int32_t*>(at(e->h_res.p, 4 * b8 + b4)),
-                     reinterpret_cast<int32_t*>(at(e->h_res.p, 4 * b8 + 2 * b4))};
-            out_d = {reinterpret_cast<double*>(at(dres, 0)), reinterpret_cast<double*>(at(dres, b8)),
-                     reinterpret_cast<double*>(at(dres, 2 * b8)), reinterpret_cast<double*>(at(dres, 3 * b8)),
-                     reinterpret_cast<int32_t*>(at(dres, 4 * b8)), reinterpret_cast<int32_t*>(at(dres, 4 * b8 + b4)),
-                     reinterpret_cast<int32_t*>(at(dres, 4 * b8 + 2 * b4))};
-        }
-    }
-    const bool dom = !(p->flags & NLDSC_FLAG_ADDITIVE_ONLY);
-    const bool strict = (p->flags & NLDSC_FLAG_STRICT_PLINK_ORDER) != 0;
-    int path = (p->flags & NLDSC_FLAG_EXACT_F4) ? 2 : (p->flags & NLDSC_FLAG_EXACT_I8) ? 1
-             : (p->flags & NLDSC_FLAG_FP32) ? 0 : e->band_mode;
-    // fp4 Gram entries are <= 16N: the segmented fp4 kernel keeps them exact in int32 up to N < 2^27
-    if (path == 2 && N >= (1 << 27)) path = 1;
-    const bool use_i8 = path != 0, use_f4 = path == 2;
-    // rows longer than one fp32-exact segment: the segmented kernel (single blocks, register strips)
-    // fp32 items pair a row block with up to 2 column blocks (2 waves / SIMD); the exact paths take one
-    const int max_nc = use_i8 ? 1 : 2;
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
+    } callers, h, d;
+    bool direct;
+    size_t b8, b4;  // bytes of an fp64 / int32 column of the owned slice
+    int n_wsum;
+    unsigned long long *wsum_h, *wsum_d;
+};
 
-    const int nb = N / 4 + (N % 4 > 0);
-    const int row_bytes = row_pitch(N);
-    const int pitch_words = row_bytes / 4;
-    const int n_it = row_bytes / CHUNK_BYTES;
-    const int nblk = (M + BLK - 1) / BLK;
-    const int Mpad = nblk * BLK;
-    // last .bed byte: bit pairs that are individuals for the reference (high pairs first,
-    // stream.h:55-66) or for PLINK (low pairs first) — the rest are recoded as missing (-> 0)
-    const int rem = N % 4;
-    uint32_t tail_keep = 0xFFu;
-    if (rem) tail_keep = strict ? (uint32_t)((1u << (2 * rem)) - 1u) : (uint32_t)(0xFFu << (8 - 2 * rem)) & 0xFFu;
+int resolve_host_out(nldsc_engine* e, const nldsc_ld_result* r, int own_begin, int own_end, HostOut* out, char* err,
+                     size_t errlen) {
+    HostOut& o = *out;
+    const int n_own = own_end - own_begin;
+    const size_t b8 = o.b8 = sizeof(double) * (size_t)n_own, b4 = o.b4 = sizeof(int32_t) * (size_t)n_own;
+    o.n_wsum = nldsc::finalize_out_blocks(n_own);
+    const size_t wsum_off = (4 * b8 + 3 * b4 + 7) / 8 * 8;
+    HIPCHK(e->h_res.ensure(wsum_off + 2 * sizeof(unsigned long long) * (size_t)o.n_wsum));
+    uint8_t* dres = nullptr;
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dres), e->h_res.p, 0));
+    o.wsum_h = reinterpret_cast<unsigned long long*>(e->h_res.p + wsum_off);
+    o.wsum_d = reinterpret_cast<unsigned long long*>(dres + wsum_off);
+    const size_t ob = (size_t)own_begin;
+    o.callers = {r->l2 + ob, r->l2d + ob, r->maf + ob, r->residuals_std + ob, r->l2_ws + ob, r->l2d_ws + ob,
+                 r->l2d_wse + ob};
+    auto reg8 = [&](double* c) { return static_cast<double*>(registered_device_ptr(c, b8)); };
+    auto reg4 = [&](int32_t* c) { return static_cast<int32_t*>(registered_device_ptr(c, b4)); };
+    const HostOut::Cols reg = {reg8(o.callers.l2), reg8(o.callers.l2d), reg8(o.callers.maf), reg8(o.callers.rstd),
+                               reg4(o.callers.wsa), reg4(o.callers.wsd), reg4(o.callers.wsde)};
+    o.direct = reg.l2 && reg.l2d && reg.maf && reg.rstd && reg.wsa && reg.wsd && reg.wsde;
+    e->last_direct = o.direct ? 1 : 0;
+    auto cols = [&](uint8_t* base) {  // the seven columns end to end in the landing buffer
+        double* c8 = reinterpret_cast<double*>(base);
+        int32_t* c4 = reinterpret_cast<int32_t*>(base + 4 * b8);
+        return HostOut::Cols{c8, c8 + n_own, c8 + 2 * n_own, c8 + 3 * n_own, c4, c4 + n_own, c4 + 2 * n_own};
+    };
+    o.h = o.direct ? o.callers : cols(e->h_res.p);
+    o.d = o.direct ? reg : cols(dres);
+    return NLDSC_OK;
+}
 
-    // the band kernels read the resident rows (Mpad rows at row_bytes pitch) in place
-    const uint32_t* geno = reinterpret_cast<const uint32_t*>(e->bed.p);
-    HIPCHK(e->counts.ensure((size_t)M * 4));
-    HIPCHK(e->cparts.ensure((size_t)M * 3));
+// the work buffers of a run, sized (allocation happens on the first run of a size; the enqueue phases allocate only
+// what depends on the schedule's counts)
+int ensure_run_buffers(nldsc_engine* e, const RunShape& s, const PlanMode& m, char* err, size_t errlen) {
+    const size_t M = (size_t)s.M;
+    HIPCHK(e->counts.ensure(M * 4));
+    HIPCHK(e->cparts.ensure(M * 3));
     HIPCHK(e->rep_count.ensure(1));  // (zeroed by the statistics kernel)
-    HIPCHK(e->lut.ensure((size_t)Mpad * 4));
-    HIPCHK(e->cst.ensure((size_t)Mpad));
-    HIPCHK(e->sflags.ensure((size_t)Mpad));
-    HIPCHK(e->blk_rep.ensure((size_t)nblk));
-    HIPCHK(e->pos.ensure((size_t)M));
-    HIPCHK(e->res.ensure(4 * (size_t)M + (3 * (size_t)M + 1) / 2));
+    HIPCHK(e->lut.ensure((size_t)s.Mpad * 4));
+    HIPCHK(e->cst.ensure((size_t)s.Mpad));
+    HIPCHK(e->sflags.ensure((size_t)s.Mpad));
+    HIPCHK(e->blk_rep.ensure((size_t)s.nblk));
+    HIPCHK(e->pos.ensure(M));
+    HIPCHK(e->res.ensure(4 * M + (3 * M + 1) / 2));
     e->l2.p = e->res.p;
     e->l2d.p = e->l2.p + M;
     e->maf.p = e->l2d.p + M;
     e->rstd.p = e->maf.p + M;
     e->ws3.p = reinterpret_cast<int*>(e->rstd.p + M);
-    HIPCHK(e->Lw.ensure((size_t)M));
-    HIPCHK(e->Rw.ensure((size_t)M));
-    HIPCHK(e->l2_acc.ensure((size_t)M));
-    HIPCHK(e->l2d_acc.ensure((size_t)M));
-    HIPCHK(e->ws_acc.ensure((size_t)M * 4));  // WSA, WSD, WSDE, non-finite flags
-
-    // band schedule: on the GPU when every position is >= 0 and sorted (the kernels run ahead of the
-    // count and the host only waits for two counters), else the host replay of the reference's pointers
-    const bool nonneg_sorted = nldsc::positions_nonneg_sorted(p->positions, M);
-    const bool sorted = nonneg_sorted || nldsc::positions_sorted(p->positions, M);
-    const bool gpu_plan = e->gpu_plan && nonneg_sorted && max_nc == 1;
-    // the 2 x 2 block-pair workgroups: fp4, unsegmented rows, GPU plan, and no K-split (choose_ksplit below); with
-    // super-item routing (t2 modes 1 and 3) only when a missing-free block exists in this run's sample order (routing
-    // takes none otherwise: C3 / C2 synthetic data, 1 % missing — the super plan, the compaction and two empty quad
-    // launches cost ~50 us per run)
-    const int order = strict ? 1 : 0;  // bit of row_miss: the individual slots of this run's sample order
-    const bool t2_cand = e->t2_mode > 0 && gpu_plan && use_f4 && n_it <= nldsc::F4_SEG_CHUNKS && n_it >= 2 &&
-                         (e->t2_mode == 2 || e->free_blocks[order] > 0);
-    // additive-only fp4 items of two column blocks (GPU plan, unsegmented rows; no K-split: its partial kernel takes
-    // single block pairs)
-    const bool nc2 = e->f4_nc2 && gpu_plan && use_f4 && !dom && n_it <= nldsc::F4_SEG_CHUNKS;
-    const bool routed = e->t2_mode == 1 || e->t2_mode == 3;
-    const bool quad = e->t2_mode == 3;
-    const int route_shift = quad ? 2 : 1;  // super-items of 2^route_shift blocks a side
-    // K-split (f4, unsegmented rows) when the items fill the wave slots (2 per SIMD) in few, partly empty
-    // rounds — a rank's shard of one chromosome — and splitting the K loop in P pieces fills them better
-    // Model: a round of items takes ~0.67 us per K chunk (C3: 2 466 chunks, 1.65 ms per round, 12.7 rounds in
-    // 20.9 ms); the split adds ~64 KiB of partial-tile traffic per piece at ~3 TB/s effective (measured: a 1/8
-    // shard of C3, 3 300 items, band 3.35 -> 3.01 ms; a 1/2 shard, 13 000 items, P = 5 made it 7.5 % slower).
-    auto choose_ksplit = [&](int n_items) {
-        int ksplit = 1;
-        if (use_f4 && !nc2 && n_items > 0 && n_it <= nldsc::F4_SEG_CHUNKS && e->ksplit_ok) {
-            const double slots = 8.0 * (double)e->n_cu, t_round = 0.67e-6 * n_it;
-            auto cost = [&](int P) {
-                return std::ceil((double)n_items * P / slots) / P * t_round +
-                       (P > 1 ? n_items * P * 65536.0 / 3e12 : 0.0);
-            };
-            double best = cost(1);
-            for (int P = 2; P <= 8 && 2 * P <= n_it; ++P)
-                if (cost(P) < 0.97 * best && (size_t)n_items * P * 32768 <= ((size_t)3 << 30)) {
-                    best = cost(P);
-                    ksplit = P;
-                }
-        }
-        return ksplit;
-    };
-    int ksplit = 1;
-    bool use_t2 = false;
-    int n_items2 = 0;
-    const bool fused_plan = gpu_plan && e->plan_fused && M <= nldsc::PLAN_SMALL_N;
-    if (gpu_plan) {
-        const size_t n_t = (size_t)(nblk + 15) / 16;
+    HIPCHK(e->Lw.ensure(M));
+    HIPCHK(e->Rw.ensure(M));
+    HIPCHK(e->l2_acc.ensure(M));
+    HIPCHK(e->l2d_acc.ensure(M));
+    HIPCHK(e->ws_acc.ensure(M * 4));  // WSA, WSD, WSDE, non-finite flags
+    if (m.gpu_plan) {
+        const size_t n_t = (size_t)(s.nblk + 15) / 16;
         // window edges A | E, then the right-pointer scan's tile maxima
-        HIPCHK(e->Aw.ensure(2 * (size_t)M + (M + 255) / 256));
-        HIPCHK(e->plan_rows.ensure((size_t)nblk));
+        HIPCHK(e->Aw.ensure(2 * M + (M + 255) / 256));
+        HIPCHK(e->plan_rows.ensure((size_t)s.nblk));
         HIPCHK(e->plan_counts.ensure(n_t * n_t));
         HIPCHK(e->plan_meta.ensure(8));  // [0, 4) single-block plan, [4, 8) super-item plan
         HIPCHK(e->h_meta.ensure(8 * sizeof(int)));
-        if (fused_plan) HIPCHK(e->items.ensure(nldsc::plan_small_items(M)));  // (emitted with the plan)
-        if (t2_cand) {
-            const size_t nblk2 = (size_t)(nblk + 1) / 2, n_t2 = (nblk2 + 15) / 16;
+        if (m.fused) HIPCHK(e->items.ensure(nldsc::plan_small_items(s.M)));  // (emitted with the plan)
+        if (m.t2_cand) {
+            const size_t nblk2 = (size_t)(s.nblk + 1) / 2, n_t2 = (nblk2 + 15) / 16;
             HIPCHK(e->plan_rows2.ensure(nblk2));
-            HIPCHK(e->plan_counts2.ensure(std::max<size_t>(n_t2 * n_t2, (size_t)nldsc::plan_super_counts(M, route_shift))));
+            HIPCHK(e->plan_counts2.ensure(
+                std::max<size_t>(n_t2 * n_t2, (size_t)nldsc::plan_super_counts(s.M, m.route_shift))));
         }
     }
+    return NLDSC_OK;
+}
 
-    auto t_start = std::chrono::steady_clock::now();
+// Everything that needs no schedule, on three streams: positions, window edges and tail counts on the main stream, the
+// plan on the plan stream beside them, then statistics, pair range, replay flags, left pointers, the blocks' missing
+// flags, and the rare-variant replay on the side stream.
+int enqueue_prologue(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m, char* err,
+                     size_t errlen) {
+    const int M = s.M;
+    hipStream_t st = e->stream, cs = e->copy_stream, ps = e->plan_stream;
+    const uint8_t* flip = e->oriented ? e->flip.p : nullptr;
     // The positions go up and the schedule's window edges are searched first (~0.02 ms: beside the count kernel, whose
     // streaming saturates HBM, those dependent loads took 0.05-0.1 ms on the critical path of short runs); then the
     // count kernel, with the rest of the schedule beside it on the plan stream.
@@ -994,46 +1002,42 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
         e->copies.copy(&seg, 1);
         HIPCHK(hipMemcpyAsync(e->pos.p, e->h_pos.p, b_pos, hipMemcpyHostToDevice, st));
     }
-    if (gpu_plan) HIPCHK(nldsc::launch_plan_edges(e->pos.p, M, p->ld_wind, e->Aw.p, e->Aw.p + M, e->plan_meta.p, st));
+    if (m.gpu_plan)
+        HIPCHK(nldsc::launch_plan_edges(e->pos.p, M, p->ld_wind, e->Aw.p, e->Aw.p + M, e->plan_meta.p, st));
     HIPCHK(hipEventRecord(e->ev_pos, st));
     // non-individual slots read as missing (0x55) for the int8 / fp32 kernels, as 00 (all fp4 planes zero) for fp4;
     // the genotype counts: the load's (every byte before the last) plus this run's last byte
-    const uint32_t pad = use_f4 ? 0x00u : 0x55u;
+    const uint32_t pad = s.use_f4 ? 0x00u : 0x55u;
     HIPCHK(hipEventRecord(e->ev[0], st));  // (count_ms: the tail kernel alone; the host total covers the above)
-    HIPCHK(nldsc::launch_tail_counts(e->bed.p, e->lastb.p, M, nb, row_bytes, tail_keep, pad, e->lcounts.p,
+    HIPCHK(nldsc::launch_tail_counts(e->bed.p, e->lastb.p, M, s.nb, s.row_bytes, s.tail_keep, pad, e->lcounts.p,
                                      1, e->cparts.p, st));  // (the load's parts add into one: load_tiled_kernel)
     HIPCHK(hipEventRecord(e->ev[1], st));
-    if (gpu_plan) {
-        HIPCHK(hipStreamWaitEvent(e->plan_stream, e->ev_pos, 0));
-        HIPCHK(nldsc::launch_plan(M, own_begin, own_end, e->Aw.p, e->Aw.p + M, e->Rw.p, e->plan_rows.p,
-                                  e->plan_counts.p, e->plan_meta.p, e->plan_stream, nc2,
-                                  fused_plan ? e->items.p : nullptr));
-        if (t2_cand)
+    if (m.gpu_plan) {
+        HIPCHK(hipStreamWaitEvent(ps, e->ev_pos, 0));
+        HIPCHK(nldsc::launch_plan(M, s.own_begin, s.own_end, e->Aw.p, e->Aw.p + M, e->Rw.p, e->plan_rows.p,
+                                  e->plan_counts.p, e->plan_meta.p, ps, m.nc2, m.fused ? e->items.p : nullptr));
+        if (m.t2_cand)
             HIPCHK(nldsc::launch_plan_super(M, e->plan_rows.p, e->plan_rows2.p, e->plan_counts2.p, e->plan_meta.p + 4,
-                                            route_shift,
-                                            e->plan_stream));
+                                            m.route_shift, ps));
         for (int k = 0; k < 8; ++k) reinterpret_cast<volatile int*>(e->h_meta.p)[k] = -1;  // (counts land >= 0)
-        HIPCHK(hipMemcpyAsync(e->h_meta.p, e->plan_meta.p, 8 * sizeof(int), hipMemcpyDeviceToHost, e->plan_stream));
-        HIPCHK(hipEventRecord(e->ev_plan, e->plan_stream));
+        HIPCHK(hipMemcpyAsync(e->h_meta.p, e->plan_meta.p, 8 * sizeof(int), hipMemcpyDeviceToHost, ps));
+        HIPCHK(hipEventRecord(e->ev_plan, ps));
     }
-    HIPCHK(nldsc::launch_snp_stats(e->cparts.p, 1, e->counts.p, e->rep_count.p,
-                                   e->oriented ? e->flip.p : nullptr, e->pos.p, M, Mpad, N, p->maf, p->std_thr,
-                                   e->lut.p, e->cst.p, e->sflags.p, e->maf.p, e->rstd.p, st, e->l2_acc.p, e->l2d_acc.p,
-                                   e->ws_acc.p, e->blk_rep.p));
+    HIPCHK(nldsc::launch_snp_stats(e->cparts.p, 1, e->counts.p, e->rep_count.p, flip, e->pos.p, M, s.Mpad, s.N, p->maf,
+                                   p->std_thr, e->lut.p, e->cst.p, e->sflags.p, e->maf.p, e->rstd.p, st, e->l2_acc.p,
+                                   e->l2d_acc.p, e->ws_acc.p, e->blk_rep.p));
     // split runs: the pairs whose lower SNP is owned (flag bit 3), before the replay may touch the flags (ev_stats)
-    if (split) HIPCHK(nldsc::launch_pair_range(e->sflags.p, M, own_begin, own_end, st));
+    if (s.split) HIPCHK(nldsc::launch_pair_range(e->sflags.p, M, s.own_begin, s.own_end, st));
     // rare variants: the reference's fp32 residual replayed (its sums assume N < 2^23); the flags per block here,
     // the replay itself after the schedule (below)
-    const bool replay = N < (1 << 23) && !(p->flags & NLDSC_FLAG_EXACT_RARE);
     // Invariant of the overlap: the replay rewrites, for replayed SNPs only, sflags bit 1 (residual pass; a byte
     // read-modify-write), cst and lut.  What runs beside it on the main stream reads sflags bits 0 (MAF pass:
     // left_pointer_kernel, the host flag copy) and 2 (missing calls: the band kernels' rm / cm), which the
     // replay never changes, and never reads a replayed SNP's cst / lut before ev_replay: the items
     // of blocks holding one are skipped (skip_item) until the KC launch, and the K-split part kernel, which runs
     // them, stores Gram tiles without reading constants.  No other kernel writes sflags after snp_stats_kernel.
-    if (replay) {
-        HIPCHK(nldsc::launch_replay_flags(e->counts.p, e->oriented ? e->flip.p : nullptr, e->sflags.p, M,
-                                          e->blk_rep.p, st, true));
+    if (s.replay) {
+        HIPCHK(nldsc::launch_replay_flags(e->counts.p, flip, e->sflags.p, M, e->blk_rep.p, st, true));
         HIPCHK(hipEventRecord(e->ev_stats, st));
     }
     HIPCHK(hipEventRecord(e->ev[2], st));
@@ -1042,80 +1046,84 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     // count), the blocks' missing flags (from the load) and the rare-variant replay — a few long sequential sums, on
     // the side stream beside the band launch for the items without a replayed SNP; only the KC launch and finalize
     // wait for it (ev_replay).  (Its sums assume N < 2^23.)
-    hipStream_t cs = e->copy_stream, ps = e->plan_stream;
-    if (gpu_plan) HIPCHK(nldsc::launch_left_pointers(e->Aw.p, e->sflags.p, e->pos.p, M, e->Lw.p, st));
-    if (use_f4) {  // per 32-SNP block: holds a missing call (the kernels' m-product predicate: routing, issued count)
-        HIPCHK(e->blk_miss.ensure((size_t)nblk));
-        HIPCHK(nldsc::launch_block_missing_rows(e->row_miss.p, M, order, e->blk_miss.p, gpu_plan ? ps : st));
+    if (m.gpu_plan) HIPCHK(nldsc::launch_left_pointers(e->Aw.p, e->sflags.p, e->pos.p, M, e->Lw.p, st));
+    if (s.use_f4) {  // per 32-SNP block: holds a missing call (the kernels' m-product predicate: routing, issued count)
+        HIPCHK(e->blk_miss.ensure((size_t)s.nblk));
+        HIPCHK(nldsc::launch_block_missing_rows(e->row_miss.p, M, s.order, e->blk_miss.p, m.gpu_plan ? ps : st));
     }
-    if (replay) {
+    if (s.replay) {
         HIPCHK(hipStreamWaitEvent(cs, e->ev_stats, 0));
-        HIPCHK(nldsc::launch_reference_residuals(e->bed.p, row_bytes, N, strict, e->counts.p,
-                                                 e->oriented ? e->flip.p : nullptr, M, p->std_thr, e->cst.p, e->lut.p,
-                                                 e->sflags.p, e->rstd.p, cs));
+        HIPCHK(nldsc::launch_reference_residuals(e->bed.p, s.row_bytes, s.N, s.strict, e->counts.p, flip, M, p->std_thr,
+                                                 e->cst.p, e->lut.p, e->sflags.p, e->rstd.p, cs));
         HIPCHK(hipEventRecord(e->ev_replay, cs));
     }
+    return NLDSC_OK;
+}
 
-    // ---- window replay + schedule ----
-    auto t_host0 = std::chrono::steady_clock::now();
-    int n_items = 0;
-    bool compact = false;
-    if (gpu_plan) {
-        {  // the count kernel is running meanwhile; the host polls the pinned counters (a blocking event wait wakes
-           // the thread tens of microseconds late: the schedule is on the critical path of short runs — a 1/8 shard,
-           // C2 — whose count ends first), then the event confirms the whole copy
-            (void)spin_until_nonneg(reinterpret_cast<volatile const int*>(e->h_meta.p) + 1);
-            HIPCHK(hipEventSynchronize(e->ev_plan));
-        }
-        const int* meta = reinterpret_cast<const int*>(e->h_meta.p);
-        n_items = meta[1];
-        ksplit = choose_ksplit(n_items);
-        // long rows: bands of at least round_min rounds of wave slots go in round launches (the last, partial round
-        // K-split), not K-split whole — a 1/8 shard of C3 (1.6 rounds) band 2.70-2.76 -> 2.61-2.64 ms, a 1/4 shard
-        // (3.2 rounds) 5.21-5.26 -> 4.87-4.89 ms (profiles/r03_ab_round_min.txt; was from 4 rounds on)
-        // — in the single-block kernel, as the K-split it replaces: a shard's few super-items leave most CUs of the
-        // 4 x 4 kernel idle (a missing-free 1/8 shard of C3: 2.88 ms with it, 1.93-1.99 K-split whole)
-        bool rounds_forced = false;
-        if (e->band_rounds && use_f4 && n_it >= 1024 && n_it <= nldsc::F4_SEG_CHUNKS &&
-            n_items >= e->round_min * 8 * e->n_cu) {
-            rounds_forced = ksplit > 1;
-            ksplit = 1;
-        }
-        use_t2 = t2_cand && ksplit == 1 && n_items > 0 && !rounds_forced;
-        // The work lists go out on the plan stream, beside the count kernel: the items, the super-items and, with
-        // super-item routing (blk_miss, above), the list of the items the single-block kernel keeps, compacted in order,
-        // so its launches (round launches, the K-split tail) are sized by its own work — its length reaches the host
-        // before the band.  The main stream waits for them.
-        if (use_t2) {
-            n_items2 = meta[5];
-            HIPCHK(e->items2.ensure(std::max<size_t>((size_t)n_items2, 1)));
-            HIPCHK(nldsc::launch_plan_emit_super(M, e->plan_rows2.p, e->plan_meta.p + 4, e->plan_counts2.p,
-                                                 e->items2.p, route_shift, ps));
-        }
-        if (!use_t2 || routed) {
-            HIPCHK(e->items.ensure(std::max<size_t>((size_t)n_items, 1)));  // (fused: already holds them)
-            if (n_items > 0 && !fused_plan)
-                HIPCHK(nldsc::launch_plan_emit(M, e->plan_rows.p, e->plan_meta.p, e->plan_counts.p, e->items.p, ps,
-                                               nc2));
-        }
-        compact = use_t2 && routed && n_items > 0;
-        if (compact) {
-            const size_t n_chunks = ((size_t)n_items + 255) / 256;  // (ld_kernels.hip COMPACT_CHUNK)
-            HIPCHK(e->items_u.ensure((size_t)n_items));
-            HIPCHK(e->compact_tmp.ensure(n_chunks + 1));
-            HIPCHK(e->h_route.ensure(sizeof(int)));
-            *reinterpret_cast<volatile int*>(e->h_route.p) = -1;  // (the copy below lands the count, >= 0)
-            HIPCHK(nldsc::launch_compact_items(e->items.p, n_items, e->blk_miss.p, route_shift,
-                                               nblk, e->compact_tmp.p,
-                                               e->compact_tmp.p + n_chunks, e->items_u.p, ps));
-            HIPCHK(hipMemcpyAsync(e->h_route.p, e->compact_tmp.p + n_chunks, sizeof(int), hipMemcpyDeviceToHost, ps));
-        }
-        HIPCHK(hipEventRecord(e->ev_route, ps));
-        HIPCHK(hipStreamWaitEvent(st, e->ev_route, 0));  // the band reads the schedule and the lists
-    } else {
+// the band's work, as the schedule decided it
+struct Schedule {
+    int n_items = 0, n_items2 = 0;  // single-block items, super-items
+    int ksplit = 1;                 // K-split of the whole band
+    bool use_t2 = false;            // the super-item kernels run
+    bool compact = false;           // the single-block kernel's items are compacted (items_u, count in h_route)
+};
+
+// The GPU plan: the host waits for its two counters, decides the kernels, and queues the work lists on the plan stream.
+int schedule_on_gpu(nldsc_engine* e, const RunShape& s, const PlanMode& m, Schedule* out, char* err, size_t errlen) {
+    Schedule& sc = *out;
+    hipStream_t ps = e->plan_stream;
+    // the count kernel is running meanwhile; the host polls the pinned counters (a blocking event wait wakes
+    // the thread tens of microseconds late: the schedule is on the critical path of short runs — a 1/8 shard,
+    // C2 — whose count ends first), then the event confirms the whole copy
+    (void)spin_until_nonneg(reinterpret_cast<volatile const int*>(e->h_meta.p) + 1);
+    HIPCHK(hipEventSynchronize(e->ev_plan));
+    const int* meta = reinterpret_cast<const int*>(e->h_meta.p);
+    sc.n_items = meta[1];
+    const nldsc::BandChoice c = nldsc::choose_band(sc.n_items, s.n_it, e->n_cu, s.use_f4,
+                                                   s.use_f4 && !m.nc2 && e->ksplit_ok, e->band_rounds, m.t2_cand);
+    sc.ksplit = c.ksplit;
+    sc.use_t2 = c.use_t2;
+    // The work lists go out on the plan stream, beside the count kernel: the items, the super-items and, with
+    // super-item routing (blk_miss), the list of the items the single-block kernel keeps, compacted in order,
+    // so its launches (round launches, the K-split tail) are sized by its own work — its length reaches the host
+    // before the band.  The main stream waits for them.
+    if (sc.use_t2) {
+        sc.n_items2 = meta[5];
+        HIPCHK(e->items2.ensure(std::max<size_t>((size_t)sc.n_items2, 1)));
+        HIPCHK(nldsc::launch_plan_emit_super(s.M, e->plan_rows2.p, e->plan_meta.p + 4, e->plan_counts2.p, e->items2.p,
+                                             m.route_shift, ps));
+    }
+    if (!sc.use_t2 || m.routed) {
+        HIPCHK(e->items.ensure(std::max<size_t>((size_t)sc.n_items, 1)));  // (fused: already holds them)
+        if (sc.n_items > 0 && !m.fused)
+            HIPCHK(nldsc::launch_plan_emit(s.M, e->plan_rows.p, e->plan_meta.p, e->plan_counts.p, e->items.p, ps,
+                                           m.nc2));
+    }
+    sc.compact = sc.use_t2 && m.routed && sc.n_items > 0;
+    if (sc.compact) {
+        const size_t n_chunks = ((size_t)sc.n_items + 255) / 256;  // (ld_kernels.hip COMPACT_CHUNK)
+        HIPCHK(e->items_u.ensure((size_t)sc.n_items));
+        HIPCHK(e->compact_tmp.ensure(n_chunks + 1));
+        HIPCHK(e->h_route.ensure(sizeof(int)));
+        *reinterpret_cast<volatile int*>(e->h_route.p) = -1;  // (the copy below lands the count, >= 0)
+        HIPCHK(nldsc::launch_compact_items(e->items.p, sc.n_items, e->blk_miss.p, m.route_shift, s.nblk,
+                                           e->compact_tmp.p, e->compact_tmp.p + n_chunks, e->items_u.p, ps));
+        HIPCHK(hipMemcpyAsync(e->h_route.p, e->compact_tmp.p + n_chunks, sizeof(int), hipMemcpyDeviceToHost, ps));
+    }
+    HIPCHK(hipEventRecord(e->ev_route, ps));
+    HIPCHK(hipStreamWaitEvent(e->stream, e->ev_route, 0));  // the band reads the schedule and the lists
+    return NLDSC_OK;
+}
+
+// The host replay of the reference's pointers and the host plan, uploaded on the main stream.
+int schedule_on_host(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m, Schedule* out,
+                     char* err, size_t errlen) {
+    const int M = s.M;
+    hipStream_t st = e->stream;
     e->h_L.resize(M);
     e->h_R.resize(M);
-    if (sorted) {
+    const uint8_t* flags = nullptr;
+    if (m.sorted) {
         // Sorted positions: nothing waits for the GPU.  The right pointers and the all-pass left
         // pointers do not depend on the MAF flags, and SNPs failing MAF only shrink the set of needed
         // block pairs (their L_j grow, their rows and columns drop), so the all-pass schedule is a
@@ -1123,26 +1131,25 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
         // pointers come from the device flags (left_pointer_kernel).  The kernels mask every pair
         // with the exact pointers.
         e->h_all_pass.assign(M, 1);
-        nldsc::replay_windows(p->positions, e->h_all_pass.data(), M, p->ld_wind, e->h_L.data(), e->h_R.data());
-        nldsc::plan_items(p->positions, e->h_all_pass.data(), M, p->ld_wind, e->h_L.data(), e->h_R.data(), own_begin,
-                   own_end, max_nc, e->h_items);
+        flags = e->h_all_pass.data();
     } else {
         // unsorted positions: the reference's sequential pointer semantics need the MAF flags first
-        e->h_flags.resize(Mpad);
-        HIPCHK(hipMemcpyAsync(e->h_flags.data(), e->sflags.p, Mpad, hipMemcpyDeviceToHost, st));
+        e->h_flags.resize(s.Mpad);
+        HIPCHK(hipMemcpyAsync(e->h_flags.data(), e->sflags.p, s.Mpad, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        nldsc::replay_windows(p->positions, e->h_flags.data(), M, p->ld_wind, e->h_L.data(), e->h_R.data());
-        nldsc::plan_items(p->positions, e->h_flags.data(), M, p->ld_wind, e->h_L.data(), e->h_R.data(), own_begin, own_end,
-                   max_nc, e->h_items);
+        flags = e->h_flags.data();
     }
+    nldsc::replay_windows(p->positions, flags, M, p->ld_wind, e->h_L.data(), e->h_R.data());
+    nldsc::plan_items(p->positions, flags, M, p->ld_wind, e->h_L.data(), e->h_R.data(), s.own_begin, s.own_end,
+                      s.max_nc, e->h_items);
     // the band kernel reads rows [32 I, 32 (J0 + nc)) of geno / lut: check before launching
-    if (pitch_words % 8 != 0 || n_it * 8 != pitch_words)
-        return set_err(err, errlen, NLDSC_E_ARG, "internal: bad row pitch %d", pitch_words);
+    if (s.pitch_words % 8 != 0 || s.n_it * 8 != s.pitch_words)
+        return set_err(err, errlen, NLDSC_E_ARG, "internal: bad row pitch %d", s.pitch_words);
     for (const nldsc::PlanItem& it : e->h_items)
-        if (it.x < 0 || it.y < it.x || (it.z != 1 && it.z != 2) || it.y + it.z > nblk)
+        if (it.x < 0 || it.y < it.x || (it.z != 1 && it.z != 2) || it.y + it.z > s.nblk)
             return set_err(err, errlen, NLDSC_E_ARG, "internal: bad work item (%d, %d, %d) for %d blocks", it.x,
-                           it.y, it.z, nblk);
-    if (max_nc == 1) nldsc::order_items_tiled(e->h_items, nblk, TILE_R, TILE_C, e->h_scratch);
+                           it.y, it.z, s.nblk);
+    if (s.max_nc == 1) nldsc::order_items_tiled(e->h_items, s.nblk, TILE_R, TILE_C, e->h_scratch);
     HIPCHK(e->items.ensure(std::max<size_t>(e->h_items.size(), 1)));
     // the plan goes up through pinned staging: a copy from pageable memory would block this thread
     // until the stream drains (the count kernel), pinned copies are queued and return at once
@@ -1151,7 +1158,7 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     std::memcpy(e->h_stage.p, e->h_L.data(), bL);
     std::memcpy(e->h_stage.p + bL, e->h_R.data(), bL);
     if (bI) std::memcpy(e->h_stage.p + 2 * bL, e->h_items.data(), bI);
-    if (sorted) {
+    if (m.sorted) {
         HIPCHK(e->Aw.ensure((size_t)M));
         HIPCHK(hipMemcpyAsync(e->Aw.p, e->h_stage.p, bL, hipMemcpyHostToDevice, st));
         HIPCHK(nldsc::launch_left_pointers(e->Aw.p, e->sflags.p, e->pos.p, M, e->Lw.p, st));
@@ -1160,153 +1167,118 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     }
     HIPCHK(hipMemcpyAsync(e->Rw.p, e->h_stage.p + bL, bL, hipMemcpyHostToDevice, st));
     if (bI) HIPCHK(hipMemcpyAsync(e->items.p, e->h_stage.p + 2 * bL, bI, hipMemcpyHostToDevice, st));
-    n_items = (int)e->h_items.size();
-    ksplit = choose_ksplit(n_items);
-    }
-    // (l2_acc, l2d_acc and ws_acc were zeroed by snp_stats_kernel)
-    auto t_host1 = std::chrono::steady_clock::now();
+    out->n_items = (int)e->h_items.size();
+    out->ksplit = nldsc::choose_ksplit(out->n_items, s.n_it, e->n_cu, s.use_f4 && !m.nc2 && e->ksplit_ok);
+    return NLDSC_OK;
+}
 
+// what every band launch of the run shares (ld_kernels.h)
+nldsc::BandArgs fill_band_args(const nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m) {
+    nldsc::BandArgs a;
+    a.geno = reinterpret_cast<const uint32_t*>(e->bed.p);  // the resident rows (Mpad rows at row_bytes pitch) in place
+    a.pitch_words = s.pitch_words, a.n_it = s.n_it, a.cst = e->cst.p, a.lut = e->lut.p;
+    a.pos = e->pos.p, a.Lw = e->Lw.p, a.Rw = e->Rw.p, a.sflags = e->sflags.p, a.n_snp = s.M;
+    a.ld_wind = p->ld_wind, a.n_org = (double)s.N, a.rsq_thr = p->rsq_thr;
+    a.own_lo = s.own_begin, a.own_hi = s.flush_hi;
+    a.l2_acc = e->l2_acc.p, a.l2d_acc = e->l2d_acc.p, a.ws_acc = e->ws_acc.p;
+    a.dom = s.dom, a.blk_rep = s.replay ? e->blk_rep.p : nullptr;
+    a.rows = e->plan_rows.p, a.nblk = s.nblk, a.route_shift = m.route_shift, a.st = e->stream;
+    return a;
+}
+
+// the single-block launches of a run: the list (compacted when routed), its shape, the routing map they drop items by
+struct SingleLaunch {
+    const int4* items;
+    int n;
+    nldsc::SingleShape shape;
+    const uint8_t* miss;
+};
+
+// which = 1: the launch for the items without a replayed SNP (beside the replay), 2: the KC launch after it
+hipError_t launch_super(nldsc_engine* e, const nldsc::BandArgs& a, const PlanMode& m, int n_items2, int which) {
+    if (m.quad)
+        return nldsc::launch_band_f4_q(a, e->items2.p, n_items2, which, e->blk_miss.p,
+                                       e->q_rounds && n_items2 >= 16 * e->n_cu ? e->n_cu : 0);
+    return nldsc::launch_band_f4_t2(a, e->items2.p, n_items2, which, m.routed ? e->blk_miss.p : nullptr);
+}
+
+hipError_t launch_single(nldsc_engine* e, const nldsc::BandArgs& a, const RunShape& s, const PlanMode& m, int ksplit,
+                         const SingleLaunch& L, int which) {
+    if (!s.use_f4) return nldsc::launch_band_i8(a, L.items, L.n, which);
+    if (ksplit > 1) return nldsc::launch_band_f4_split(a, ksplit, L.items, L.n, e->gram.p, which, nullptr);
+    const int n_full = L.shape.n_full, per = m.nc2 ? 2 : 1;
+    const bool dfr = L.shape.defer && n_full > 0;
+    const nldsc::DeferredEpi rep = {e->rep_gram.p, e->rep_items.p, e->rep_count.p};
+    hipError_t r = nldsc::launch_band_f4(a, per, L.items, n_full, which, L.miss, L.shape.round_items,
+                                         dfr ? &rep : nullptr);
+    if (r == hipSuccess && dfr && (which & 2))  // after the replay: the deferred items' epilogues
+        r = nldsc::launch_band_f4_deferred_epi(a, n_full * per, rep);
+    if (r != hipSuccess || n_full == L.n) return r;
+    return nldsc::launch_band_f4_split(a, L.shape.tail_p, L.items + n_full, L.n - n_full, e->gram.p, which, L.miss);
+}
+
+// The band on the main stream (ev[3] .. ev[4]): the super-item launch, the wait for the compacted count, the
+// single-block launches, the KC launches after the replay (ev_replay), or the fp32 launch; then the issued-product
+// count on the side stream (ev_issued).
+int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m, const Schedule& sc,
+                 char* err, size_t errlen) {
+    hipStream_t st = e->stream, cs = e->copy_stream;
+    const int n_items = sc.n_items;
     HIPCHK(hipEventRecord(e->ev[3], st));
     e->n_band_items = n_items;
-    e->last_ksplit = ksplit;
-    e->last_band_kernel = use_t2 ? (quad ? NLDSC_BAND_F4_QUAD : routed ? NLDSC_BAND_F4_ROUTED : NLDSC_BAND_F4_2X2) : !use_f4 ? (use_i8 ? NLDSC_BAND_I8 : NLDSC_BAND_F32)
-                        : ksplit > 1 ? NLDSC_BAND_F4_KSPLIT : n_it > nldsc::F4_SEG_CHUNKS ? NLDSC_BAND_F4_SEG
-                        : NLDSC_BAND_F4;
-    if (ksplit > 1) HIPCHK(e->gram.ensure((size_t)n_items * ksplit * 8192));
-    const int slots = 8 * e->n_cu;
-    // which = 1: the launch for the items without a replayed SNP (beside the replay), 2: the KC launch after it
-    const uint8_t* blk_rep = replay ? e->blk_rep.p : nullptr;
-    int n_single = n_items;            // single-block items (compacted when routed)
-    const int4* single = e->items.p;
-    int round_items = 0, tail_p = 1, n_full = 0;
-    // Unsegmented single-block fp4 items go in launches of one round of the wave slots each (2 per SIMD): the items
-    // of a launch start together and, all of equal length, stay at nearby K offsets, so the waves on one XCD that
-    // share a strip (the plan's 16 x 16 tiles) read it from that XCD's L2.  In one launch of all items the waves
-    // drift apart and most strip bytes come from beyond L2 again (C3: 68 -> 14 GB per band, the clock 1.90 -> 2.02
-    // GHz; band -2 to -4 % after the launch tails).  From one round of items on (round_min), only for long rows: the
-    // waves of a round also reach their epilogues together, which then no longer overlap another wave's products —
-    // at N = 50 000 (strips of 0.4 MB, L2-resident anyway; epilogue ~1/3 of an item) round launches made the band
-    // 2.8 -> 5.1 ms.  The last, partial round leaves wave slots idle for a whole item length (C3: 1 458 items in
-    // 2 048 slots); those items are K-split instead when the cost model finds it cheaper (C3: P = 7, 5 rounds of 1/7
-    // of an item).
-    // rare-variant items of the single-block fp4 kernel run their K loops in the main launch (Gram tiles kept), their
-    // epilogues after the replay (launch_band_f4 rep_gram): unsegmented rows, no K-split of the whole band (whose
-    // partial kernel already runs every item)
-    bool defer = replay && e->defer_rep && use_f4 && ksplit == 1 && n_it <= nldsc::F4_SEG_CHUNKS;
-    auto size_single = [&]() -> hipError_t {
-        round_items = use_f4 && ksplit == 1 && e->band_rounds && n_it <= nldsc::F4_SEG_CHUNKS &&
-                      n_it >= 1024 && n_single >= e->round_min * slots ? slots : 0;
-        const int tail = round_items > 0 ? n_single % round_items : 0;
-        tail_p = tail > 0 ? choose_ksplit(tail) : 1;
-        n_full = tail_p > 1 ? n_single - tail : n_single;
-        e->last_round_items = round_items;
-        e->last_tail_ksplit = tail_p;
-        // slots for every block pair of the main launch (an upper bound: which items hold a replayed SNP is known on
-        // the device only); past REP_GRAM_MAX_SLOTS (32 KiB each) the KC launch after the replay runs those items
-        // instead (a wide band of data with missing calls, where nearly every item stays in this kernel: ADVICE r03)
-        if (defer && (size_t)n_full * (nc2 ? 2 : 1) > e->rep_gram_max_slots) defer = false;
-        if (defer && n_full > 0) {
-            const size_t slots = (size_t)n_full * (nc2 ? 2 : 1);
-            hipError_t r = e->rep_gram.ensure(slots * 8192);
-            if (r == hipSuccess) r = e->rep_items.ensure(slots);
-            if (r != hipSuccess) return r;
-        }
-        return tail_p > 1 ? e->gram.ensure((size_t)tail * tail_p * 8192) : hipSuccess;
-    };
-    // per-SNP sums accumulate for the owned SNPs, or (split runs) for every SNP from own_begin on (the right halo's to
-    // be exported)
-    const int flush_hi = split ? M : own_end;
-    auto launch_super = [&](int which) -> hipError_t {
-        if (quad)
-            return nldsc::launch_band_f4_q(dom, n_items2, geno, pitch_words, n_it, e->cst.p, e->items2.p,
-                                           e->plan_rows.p, nblk, e->pos.p, e->Lw.p, e->Rw.p, e->sflags.p, M,
-                                           p->ld_wind, (double)N, p->rsq_thr, own_begin, flush_hi, e->l2_acc.p,
-                                           e->l2d_acc.p, e->ws_acc.p, true, blk_rep, e->blk_miss.p, which, st,
-                                           e->q_rounds && n_items2 >= 16 * e->n_cu ? e->n_cu : 0);
-        return nldsc::launch_band_f4_t2(
-            dom, n_items2, geno, pitch_words, n_it, e->cst.p, e->items2.p, e->plan_rows.p, nblk, e->pos.p, e->Lw.p,
-            e->Rw.p, e->sflags.p, M, p->ld_wind, (double)N, p->rsq_thr, own_begin, flush_hi, e->l2_acc.p, e->l2d_acc.p,
-            e->ws_acc.p, true, blk_rep, routed ? e->blk_miss.p : nullptr, which, st);
-    };
+    e->last_ksplit = sc.ksplit;
+    e->last_band_kernel = nldsc::band_kernel_code(sc.use_t2, e->t2_mode, s.path, sc.ksplit, s.n_it);
+    if (sc.ksplit > 1) HIPCHK(e->gram.ensure((size_t)n_items * sc.ksplit * 8192));
+    const nldsc::BandArgs a = fill_band_args(e, p, s, m);
     // (column-block pair items: the compaction keeps an item while one of its blocks is unrouted, the kernel drops
     // the other)
-    const uint8_t* single_miss =
-        use_t2 && routed && (!compact || nc2) ? e->blk_miss.p : nullptr;
-    auto launch_single = [&](int which) -> hipError_t {
-        if (use_f4 && ksplit > 1)
-            return nldsc::launch_band_f4_split(dom, ksplit, n_single, geno, pitch_words, n_it, e->cst.p, single,
-                                               e->pos.p, e->Lw.p, e->Rw.p, e->sflags.p, M, p->ld_wind, (double)N,
-                                               p->rsq_thr, own_begin, flush_hi, e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p,
-                                               blk_rep, e->gram.p, which, st);
-        if (use_f4) {
-            const bool dfr = defer && n_full > 0;
-            hipError_t r = nldsc::launch_band_f4(dom, nc2 ? 2 : 1, n_full, geno, pitch_words, n_it, e->cst.p, single,
-                                                 e->pos.p, e->Lw.p, e->Rw.p, e->sflags.p, M, p->ld_wind, (double)N,
-                                                 p->rsq_thr, own_begin, flush_hi, e->l2_acc.p, e->l2d_acc.p,
-                                                 e->ws_acc.p, true, blk_rep, which, st, single_miss, round_items,
-                                                 route_shift,
-                                                 dfr ? e->rep_gram.p : nullptr, dfr ? e->rep_items.p : nullptr,
-                                                 dfr ? e->rep_count.p : nullptr);
-            if (r == hipSuccess && dfr && (which & 2))  // after the replay: the deferred items' epilogues
-                r = nldsc::launch_band_f4_deferred_epi(dom, n_full * (nc2 ? 2 : 1), e->cst.p, e->rep_items.p,
-                                                       e->rep_count.p, e->rep_gram.p, e->pos.p, e->Lw.p, e->Rw.p,
-                                                       e->sflags.p, M, p->ld_wind, (double)N, p->rsq_thr, own_begin,
-                                                       flush_hi, e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, blk_rep, st);
-            if (r != hipSuccess || n_full == n_single) return r;
-            return nldsc::launch_band_f4_split(dom, tail_p, n_single - n_full, geno, pitch_words, n_it, e->cst.p,
-                                               single + n_full, e->pos.p, e->Lw.p, e->Rw.p, e->sflags.p, M,
-                                               p->ld_wind, (double)N, p->rsq_thr, own_begin, flush_hi, e->l2_acc.p,
-                                               e->l2d_acc.p, e->ws_acc.p, blk_rep, e->gram.p, which, st, single_miss,
-                                               route_shift);
-        }
-        return nldsc::launch_band_i8(dom, max_nc, n_single, geno, pitch_words, n_it, e->cst.p, single, e->pos.p,
-                                     e->Lw.p, e->Rw.p, e->sflags.p, M, p->ld_wind, (double)N, p->rsq_thr, own_begin,
-                                     flush_hi, e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, true, blk_rep, which, st);
-    };
-    const bool run_single = !use_t2 || routed;  // (option t2 = 2: every block pair in the 2 x 2 workgroups)
-    if (n_items > 0 && (use_f4 || use_i8)) {
-        if (use_t2) HIPCHK(launch_super(1));
-        if (e->debug_timing) HIPCHK(hipEventRecord(e->ev_dbg[0], st));
-        const auto t_wait0 = std::chrono::steady_clock::now();
-        if (compact) {  // the super-item kernel is queued: the host waits for the compacted count meanwhile
-            // (polling the pinned word the copy lands in: a blocking event wait wakes the thread tens of
-            // microseconds late, time the GPU would idle when the super-item kernel has nothing to do)
-            volatile int* cnt = reinterpret_cast<volatile int*>(e->h_route.p);
-            (void)spin_until_nonneg(cnt);
-            HIPCHK(hipEventSynchronize(e->ev_route));  // (returns at once when the count has landed)
-            n_single = *cnt;
-            single = e->items_u.p;
-        } else if (use_t2 && routed) {
-            single = e->items.p;  // (no compaction: every item listed, the routed ones return at once)
-        }
-        HIPCHK(size_single());
-        const auto t_wait1 = std::chrono::steady_clock::now();
+    const uint8_t* single_miss = sc.use_t2 && m.routed && (!sc.compact || m.nc2) ? e->blk_miss.p : nullptr;
+    SingleLaunch L = {e->items.p, n_items, {}, single_miss};
+    const bool exact = n_items > 0 && (s.use_f4 || s.use_i8);
+    const bool run_single = !sc.use_t2 || m.routed;  // (option t2 = 2: every block pair in the 2 x 2 workgroups)
+    if (exact && sc.use_t2) HIPCHK(launch_super(e, a, m, sc.n_items2, 1));
+    if (exact && e->debug_timing) HIPCHK(hipEventRecord(e->ev_dbg[0], st));
+    const auto t_wait0 = Clock::now();
+    if (exact && sc.compact) {  // the super-item kernel is queued: the host waits for the compacted count meanwhile
+        // (polling the pinned word the copy lands in: a blocking event wait wakes the thread tens of
+        // microseconds late, time the GPU would idle when the super-item kernel has nothing to do)
+        volatile int* cnt = reinterpret_cast<volatile int*>(e->h_route.p);
+        (void)spin_until_nonneg(cnt);
+        HIPCHK(hipEventSynchronize(e->ev_route));  // (returns at once when the count has landed)
+        L.n = *cnt;
+        L.items = e->items_u.p;
+    }  // (routed without compaction: every item listed, the routed ones return at once)
+    // the single-block launches sized by their own work (nldsc::shape_single), and their buffers
+    L.shape = nldsc::shape_single(L.n, s.n_it, e->n_cu, s.use_f4, sc.ksplit, e->band_rounds, m.nc2, e->ksplit_ok,
+                                  s.replay && e->defer_rep, e->rep_gram_max_slots);
+    e->last_round_items = L.shape.round_items;
+    e->last_tail_ksplit = L.shape.tail_p;
+    if (L.shape.defer && L.shape.n_full > 0) {
+        const size_t slots = (size_t)L.shape.n_full * (m.nc2 ? 2 : 1);
+        HIPCHK(e->rep_gram.ensure(slots * 8192));
+        HIPCHK(e->rep_items.ensure(slots));
+    }
+    if (L.shape.tail_p > 1) HIPCHK(e->gram.ensure((size_t)(L.n - L.shape.n_full) * L.shape.tail_p * 8192));
+    const auto t_wait1 = Clock::now();
+    if (exact) {
         if (e->debug_timing) HIPCHK(hipEventRecord(e->ev_dbg[1], st));
-        if (run_single) HIPCHK(launch_single(1));
+        if (run_single) HIPCHK(launch_single(e, a, s, m, sc.ksplit, L, 1));
         if (e->debug_timing) {
             HIPCHK(hipStreamSynchronize(st));
-            float a = 0, b = 0;
-            HIPCHK(hipEventElapsedTime(&a, e->ev[3], e->ev_dbg[0]));
-            HIPCHK(hipEventElapsedTime(&b, e->ev_dbg[0], e->ev_dbg[1]));
+            float t_super = 0, t_gap = 0;
+            HIPCHK(hipEventElapsedTime(&t_super, e->ev[3], e->ev_dbg[0]));
+            HIPCHK(hipEventElapsedTime(&t_gap, e->ev_dbg[0], e->ev_dbg[1]));
             std::fprintf(stderr, "[nldsc debug] super %.3f ms, gap to single %.3f ms, host wait %.3f ms, n_single %d/%d\n",
-                         a, b, std::chrono::duration<double, std::milli>(t_wait1 - t_wait0).count(), n_single, n_items);
+                         t_super, t_gap, ms_between(t_wait0, t_wait1), L.n, n_items);
         }
-        if (replay) {
-            HIPCHK(hipStreamWaitEvent(st, e->ev_replay, 0));
-            if (use_t2) HIPCHK(launch_super(2));
-            if (run_single) HIPCHK(launch_single(2));
-        }
-    } else {
-        HIPCHK(size_single());
-        if (replay) HIPCHK(hipStreamWaitEvent(st, e->ev_replay, 0));  // the fp32 path reads the replayed tables
     }
-    if (n_items > 0 && !use_f4 && !use_i8) {
-        HIPCHK(nldsc::launch_band(dom, 2, n_items, geno, pitch_words, n_it,
-                                      e->lut.p, e->items.p, e->pos.p, e->Lw.p, e->Rw.p, e->sflags.p, M, p->ld_wind,
-                                      (double)N, p->rsq_thr, own_begin, flush_hi, e->l2_acc.p, e->l2d_acc.p,
-                                      e->ws_acc.p, st));
+    if (s.replay) {  // the KC launches, and the fp32 path, read the replayed tables
+        HIPCHK(hipStreamWaitEvent(st, e->ev_replay, 0));
+        if (exact && sc.use_t2) HIPCHK(launch_super(e, a, m, sc.n_items2, 2));
+        if (exact && run_single) HIPCHK(launch_single(e, a, s, m, sc.ksplit, L, 2));
     }
-    e->last_path = path;
+    if (n_items > 0 && !s.use_f4 && !s.use_i8) HIPCHK(nldsc::launch_band(a, 2, e->items.p, n_items));
+    e->last_path = s.path;
     HIPCHK(hipEventRecord(e->ev[4], st));
     // matrix-core products the band kernels issued, counted on the GPU per work item as each kernel decides them
     // (missing-free blocks skip the m products, diagonal blocks the transposed ones, routed items run in the 2 x 2
@@ -1316,109 +1288,29 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     HIPCHK(e->h_sums.ensure(3 * sizeof(unsigned long long)));
     HIPCHK(hipStreamWaitEvent(cs, e->ev[3], 0));
     HIPCHK(hipMemsetAsync(e->sums.p + 2, 0, sizeof(unsigned long long), cs));
-    HIPCHK(nldsc::launch_issued_products(single, run_single ? n_single : 0, use_t2 ? e->items2.p : nullptr,
-                                         n_items2, gpu_plan ? e->plan_rows.p : nullptr,
-                                         use_f4 ? e->blk_miss.p : nullptr, nblk, path, dom,
-                                         (use_t2 && routed ? 2 : 0) | (single_miss != nullptr ? 1 : 0), route_shift,
+    HIPCHK(nldsc::launch_issued_products(L.items, run_single ? L.n : 0, sc.use_t2 ? e->items2.p : nullptr, sc.n_items2,
+                                         m.gpu_plan ? e->plan_rows.p : nullptr, s.use_f4 ? e->blk_miss.p : nullptr,
+                                         s.nblk, s.path, s.dom,
+                                         (sc.use_t2 && m.routed ? 2 : 0) | (L.miss != nullptr ? 1 : 0), m.route_shift,
                                          e->sums.p + 2, cs));
     HIPCHK(hipMemcpyAsync(e->h_sums.p + 2 * sizeof(unsigned long long), e->sums.p + 2, sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, cs));
     HIPCHK(hipEventRecord(e->ev_issued, cs));
-    if (split) {  // the right halo's sums out; finalize waits for the left neighbour's (run_device_finish)
-        HIPCHK(nldsc::launch_export_acc(e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, M, own_end, M, export_dev, st));
-        HIPCHK(hipStreamSynchronize(st));
-        *export_n = M - own_end;
-        float f = 0;
-        HIPCHK(hipEventElapsedTime(&f, e->ev[0], e->ev[1])); e->ms[0] = f;
-        HIPCHK(hipEventElapsedTime(&f, e->ev[1], e->ev[2])); e->ms[1] = f;
-        e->ms[2] = std::chrono::duration<double, std::milli>(t_host1 - t_host0).count();
-        HIPCHK(hipEventElapsedTime(&f, e->ev[3], e->ev[4])); e->ms[3] = f;
-        e->split_ms1 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        e->split_pending = true;
-        e->split_M = M;
-        e->split_N = N;
-        e->split_dom = dom;
-        e->split_own = {own_begin, own_end};
-        e->split_row_bytes = row_bytes;
-        e->split_table = table_dev;
-        e->split_width = width;
-        return NLDSC_OK;
-    }
-    double sw = 0, sd = 0;
-    if (table_dev) {
-        // the owned slice stays on the device (the caller gathers it device to device); only the pair counts of
-        // the metric come back
-        HIPCHK(nldsc::launch_finalize(e->Lw.p, e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, M, own_begin, own_end, dom,
-                                      e->l2.p, e->l2d.p, e->ws3.p, st));
-        HIPCHK(hipEventRecord(e->ev[5], st));
-        HIPCHK(hipMemsetAsync(e->sums.p, 0, 2 * sizeof(unsigned long long), st));
-        HIPCHK(nldsc::launch_pack_table(e->l2.p, e->l2d.p, e->maf.p, e->rstd.p, e->ws3.p, M, own_begin, own_end, width,
-                                        table_dev, e->sums.p, st));
-        HIPCHK(hipMemcpyAsync(e->h_sums.p, e->sums.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const unsigned long long* s = reinterpret_cast<const unsigned long long*>(e->h_sums.p);
-        sw = (double)s[0];
-        sd = dom ? (double)s[1] : 0.0;
-    } else {
-        // Host results: finalize writes the owned slice's seven columns straight into host memory (out_d) with its
-        // per-workgroup pair-count sums — no pack kernel, no copy engine (the runtime moves device-to-pinned copies
-        // with blit kernels: a 0.6 MB RSTD copy beside the C2 band took ~1 ms of its CU slots); without `direct`, the
-        // host copies them from the landing buffer to the caller's arrays.
-        HIPCHK(nldsc::launch_finalize_out(e->Lw.p, e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, e->maf.p, e->rstd.p, M,
-                                          own_begin, own_end, dom, out_d.l2, out_d.l2d, out_d.maf, out_d.rstd,
-                                          out_d.wsa, out_d.wsd, out_d.wsde, wsum_d, st));
-        HIPCHK(hipEventRecord(e->ev[5], st));
-        const size_t o = own_begin;
-        using clk = std::chrono::steady_clock;
-        clk::time_point tq[5];
-        tq[2] = clk::now();
-        HIPCHK(hipStreamSynchronize(st));
-        tq[3] = clk::now();
-        if (!direct) {
-            const CopyPool::Seg segs[7] = {{r->l2 + o, out_h.l2, b8},           {r->l2d + o, out_h.l2d, b8},
-                                           {r->maf + o, out_h.maf, b8},         {r->residuals_std + o, out_h.rstd, b8},
-                                           {r->l2_ws + o, out_h.wsa, b4},       {r->l2d_ws + o, out_h.wsd, b4},
-                                           {r->l2d_wse + o, out_h.wsde, b4}};
-            e->copies.copy(segs, 7);
-        }
-        unsigned long long ta = 0, td = 0;
-        for (int b = 0; b < n_wsum; ++b) {
-            ta += wsum_h[2 * b];
-            td += wsum_h[2 * b + 1];
-        }
-        sw = (double)ta;
-        sd = dom ? (double)td : 0.0;
-        tq[4] = clk::now();
-        if (e->debug_timing) {
-            auto ms = [&](int a, int b) { return std::chrono::duration<double, std::milli>(tq[b] - tq[a]).count(); };
-            std::fprintf(stderr, "[nldsc debug] host results (%s): band wait %.3f, copies and sums %.3f ms\n",
-                         direct ? "direct" : "landing buffer", ms(2, 3), ms(3, 4));
-        }
-    }
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        HIPCHK(hipEventSynchronize(e->ev_issued));
-        if (e->debug_timing)
-            std::fprintf(stderr, "[nldsc debug] issued-count wait %.3f ms\n",
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    }
-    auto t_end = std::chrono::steady_clock::now();
+    return NLDSC_OK;
+}
 
+// ms[0..3] of a run: count, statistics (GPU events), the host's wait for the schedule, the band (GPU events)
+int record_band_timings(nldsc_engine* e, double host_plan_ms, char* err, size_t errlen) {
     float f = 0;
     HIPCHK(hipEventElapsedTime(&f, e->ev[0], e->ev[1])); e->ms[0] = f;
     HIPCHK(hipEventElapsedTime(&f, e->ev[1], e->ev[2])); e->ms[1] = f;
-    e->ms[2] = std::chrono::duration<double, std::milli>(t_host1 - t_host0).count();
+    e->ms[2] = host_plan_ms;
     HIPCHK(hipEventElapsedTime(&f, e->ev[3], e->ev[4])); e->ms[3] = f;
-    HIPCHK(hipEventElapsedTime(&f, e->ev[4], e->ev[5])); e->ms[4] = f;
-    e->ms[5] = std::chrono::duration<double, std::milli>(t_end - t_start).count();
-    if (e->debug_timing) {  // where a run's wall time goes: GPU stages, the gap before the band, host tail
-        float g23 = 0, g05 = 0;
-        HIPCHK(hipEventElapsedTime(&g23, e->ev[2], e->ev[3]));
-        HIPCHK(hipEventElapsedTime(&g05, e->ev[0], e->ev[5]));
-        std::fprintf(stderr, "[nldsc debug] count %.3f stats %.3f gap-to-band %.3f band %.3f finalize %.3f | GPU span %.3f, "
-                     "host total %.3f (host wait for the plan %.3f)\n", e->ms[0], e->ms[1], g23, e->ms[3], e->ms[4], g05,
-                     e->ms[5], e->ms[2]);
-    }
+    return NLDSC_OK;
+}
+
+// the metrics of a run from its pair counts (sw = sum of positive WSA, sd = of WSD) and h_sums[2] (products issued)
+void record_metrics(nldsc_engine* e, double sw, double sd, int N, int row_bytes) {
     e->flop_issued = (double)reinterpret_cast<const unsigned long long*>(e->h_sums.p)[2] * 2.0 * BLK * BLK *
                      (double)row_bytes * 4.0;
     e->pairs = sw;
@@ -1427,6 +1319,127 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     // exact formulation: 4 integer dot products per unordered additive pair (xx, xo, ox, oo) and
     // 2 per ordered dominance pair (xh, oh): 2N (4 * 1/2 sum WSA + 2 sum WSD) int8 ops
     e->ops_alg_i8 = 2.0 * (double)N * (2.0 * sw + 2.0 * sd);
+}
+
+// Device-table runs (e->split names the table): the owned slice stays on the device (the caller gathers it device to
+// device); only the pair counts of the metric come back.  Finalize (.. ev[5]), pack, the sums copy, and the sync.
+int finish_table(nldsc_engine* e, double* sw, double* sd, char* err, size_t errlen) {
+    const nldsc_engine::SplitState& t = e->split;
+    hipStream_t st = e->stream;
+    HIPCHK(nldsc::launch_finalize(e->Lw.p, e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, t.M, t.own_lo, t.own_hi, t.dom,
+                                  e->l2.p, e->l2d.p, e->ws3.p, st));
+    HIPCHK(hipEventRecord(e->ev[5], st));
+    HIPCHK(hipMemsetAsync(e->sums.p, 0, 2 * sizeof(unsigned long long), st));
+    HIPCHK(nldsc::launch_pack_table(e->l2.p, e->l2d.p, e->maf.p, e->rstd.p, e->ws3.p, t.M, t.own_lo, t.own_hi, t.width,
+                                    t.table, e->sums.p, st));
+    HIPCHK(hipMemcpyAsync(e->h_sums.p, e->sums.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const unsigned long long* sums = reinterpret_cast<const unsigned long long*>(e->h_sums.p);
+    *sw = (double)sums[0];
+    *sd = t.dom ? (double)sums[1] : 0.0;
+    return NLDSC_OK;
+}
+
+// Host results: finalize writes the owned slice's seven columns straight into host memory (o.d) with its
+// per-workgroup pair-count sums — no pack kernel, no copy engine (the runtime moves device-to-pinned copies
+// with blit kernels: a 0.6 MB RSTD copy beside the C2 band took ~1 ms of its CU slots); without `direct`, the
+// host copies them from the landing buffer to the caller's arrays.
+int finish_host(nldsc_engine* e, const RunShape& s, const HostOut& o, double* sw, double* sd, char* err,
+                size_t errlen) {
+    hipStream_t st = e->stream;
+    HIPCHK(nldsc::launch_finalize_out(e->Lw.p, e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, e->maf.p, e->rstd.p, s.M,
+                                      s.own_begin, s.own_end, s.dom, o.d.l2, o.d.l2d, o.d.maf, o.d.rstd, o.d.wsa,
+                                      o.d.wsd, o.d.wsde, o.wsum_d, st));
+    HIPCHK(hipEventRecord(e->ev[5], st));
+    const auto t0 = Clock::now();
+    HIPCHK(hipStreamSynchronize(st));
+    const auto t1 = Clock::now();
+    if (!o.direct) {
+        const CopyPool::Seg segs[7] = {{o.callers.l2, o.h.l2, o.b8},     {o.callers.l2d, o.h.l2d, o.b8},
+                                       {o.callers.maf, o.h.maf, o.b8},   {o.callers.rstd, o.h.rstd, o.b8},
+                                       {o.callers.wsa, o.h.wsa, o.b4},   {o.callers.wsd, o.h.wsd, o.b4},
+                                       {o.callers.wsde, o.h.wsde, o.b4}};
+        e->copies.copy(segs, 7);
+    }
+    unsigned long long ta = 0, td = 0;
+    for (int b = 0; b < o.n_wsum; ++b) {
+        ta += o.wsum_h[2 * b];
+        td += o.wsum_h[2 * b + 1];
+    }
+    *sw = (double)ta;
+    *sd = s.dom ? (double)td : 0.0;
+    if (e->debug_timing)
+        std::fprintf(stderr, "[nldsc debug] host results (%s): band wait %.3f, copies and sums %.3f ms\n",
+                     o.direct ? "direct" : "landing buffer", ms_between(t0, t1), ms_between(t1, Clock::now()));
+    return NLDSC_OK;
+}
+
+// The hot path of one run.  Results go to the host arrays of `r`, or (table_dev != nullptr) stay in device memory
+// as the owned slice of the score table (nldsc_engine_run_device).
+// Split runs (nldsc_engine_run_device_split, export_n != nullptr): only the pairs whose lower SNP is owned are computed,
+// the per-SNP sums of every SNP of the slice accumulate, the right halo's [own_end, M) go out to export_dev and the run
+// stops before finalize; nldsc_engine_run_device_finish adds the left neighbour's export and finishes.
+int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end, nldsc_ld_result* r,
+             double* table_dev, int32_t width, char* err, size_t errlen, long long* export_dev = nullptr,
+             int32_t export_cap = 0, int32_t* export_n = nullptr) {
+    const bool split = export_n != nullptr;
+    int rc = check_run_args(e, p, own_begin, own_end, r, table_dev, width, split, export_dev, export_cap, err, errlen);
+    if (rc) return rc;
+    if (own_begin == own_end) return run_nothing_owned(e, p->n_snp, own_begin, table_dev, width, err, errlen);
+    HIPCHK(hipSetDevice(e->device));
+    HostOut out = {};
+    e->last_direct = -1;
+    if (!table_dev && (rc = resolve_host_out(e, r, own_begin, own_end, &out, err, errlen))) return rc;
+    const RunShape s = run_shape(e, p, own_begin, own_end, split);
+    const PlanMode m = plan_mode(e, p, s);
+    if ((rc = ensure_run_buffers(e, s, m, err, errlen))) return rc;
+
+    const auto t_start = Clock::now();
+    if ((rc = enqueue_prologue(e, p, s, m, err, errlen))) return rc;
+    // ---- window replay + schedule ----
+    const auto t_host0 = Clock::now();
+    Schedule sc;
+    rc = m.gpu_plan ? schedule_on_gpu(e, s, m, &sc, err, errlen) : schedule_on_host(e, p, s, m, &sc, err, errlen);
+    if (rc) return rc;
+    // (l2_acc, l2d_acc and ws_acc were zeroed by snp_stats_kernel)
+    const auto t_host1 = Clock::now();
+    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen))) return rc;
+
+    if (table_dev) e->split = {false, s.M, s.N, s.row_bytes, width, own_begin, own_end, s.dom, table_dev, 0.0};
+    if (split) {  // the right halo's sums out; finalize waits for the left neighbour's (run_device_finish)
+        HIPCHK(nldsc::launch_export_acc(e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, s.M, own_end, s.M, export_dev,
+                                        e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        *export_n = s.M - own_end;
+        if ((rc = record_band_timings(e, ms_between(t_host0, t_host1), err, errlen))) return rc;
+        e->split.ms1 = ms_between(t_start, Clock::now());
+        e->split.pending = true;
+        return NLDSC_OK;
+    }
+    double sw = 0, sd = 0;
+    rc = table_dev ? finish_table(e, &sw, &sd, err, errlen) : finish_host(e, s, out, &sw, &sd, err, errlen);
+    if (rc) return rc;
+    {
+        const auto t0 = Clock::now();
+        HIPCHK(hipEventSynchronize(e->ev_issued));
+        if (e->debug_timing)
+            std::fprintf(stderr, "[nldsc debug] issued-count wait %.3f ms\n", ms_between(t0, Clock::now()));
+    }
+    const auto t_end = Clock::now();
+
+    if ((rc = record_band_timings(e, ms_between(t_host0, t_host1), err, errlen))) return rc;
+    float f = 0;
+    HIPCHK(hipEventElapsedTime(&f, e->ev[4], e->ev[5])); e->ms[4] = f;
+    e->ms[5] = ms_between(t_start, t_end);
+    if (e->debug_timing) {  // where a run's wall time goes: GPU stages, the gap before the band, host tail
+        float g23 = 0, g05 = 0;
+        HIPCHK(hipEventElapsedTime(&g23, e->ev[2], e->ev[3]));
+        HIPCHK(hipEventElapsedTime(&g05, e->ev[0], e->ev[5]));
+        std::fprintf(stderr, "[nldsc debug] count %.3f stats %.3f gap-to-band %.3f band %.3f finalize %.3f | GPU span %.3f, "
+                     "host total %.3f (host wait for the plan %.3f)\n", e->ms[0], e->ms[1], g23, e->ms[3], e->ms[4], g05,
+                     e->ms[5], e->ms[2]);
+    }
+    record_metrics(e, sw, sd, s.N, s.row_bytes);
     return NLDSC_OK;
 }
 
@@ -1457,37 +1470,25 @@ int nldsc_engine_run_device_split(nldsc_engine* e, const nldsc_ld_params* p, int
 int nldsc_engine_run_device_finish(nldsc_engine* e, const int64_t* import_dev, int32_t import_n, char* err,
                                    size_t errlen) {
     if (!e) return set_err(err, errlen, NLDSC_E_ARG, "NULL engine");
-    if (!e->split_pending) return set_err(err, errlen, NLDSC_E_ARG, "no split run to finish");
-    const int32_t M = e->split_M, lo = e->split_own.first, hi = e->split_own.second;
-    if (import_n < 0 || import_n > hi - lo || (import_n > 0 && !import_dev))
-        return set_err(err, errlen, NLDSC_E_ARG, "import of %d SNPs into an owned range of %d", import_n, hi - lo);
-    e->split_pending = false;
+    if (!e->split.pending) return set_err(err, errlen, NLDSC_E_ARG, "no split run to finish");
+    const int32_t own = e->split.own_hi - e->split.own_lo;
+    if (import_n < 0 || import_n > own || (import_n > 0 && !import_dev))
+        return set_err(err, errlen, NLDSC_E_ARG, "import of %d SNPs into an owned range of %d", import_n, own);
+    e->split.pending = false;
     HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(nldsc::launch_import_acc(e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, M, lo, import_n,
-                                    reinterpret_cast<const long long*>(import_dev), st));
-    HIPCHK(hipEventRecord(e->ev[4], st));
-    HIPCHK(nldsc::launch_finalize(e->Lw.p, e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, M, lo, hi, e->split_dom, e->l2.p,
-                                  e->l2d.p, e->ws3.p, st));
-    HIPCHK(hipEventRecord(e->ev[5], st));
-    HIPCHK(hipMemsetAsync(e->sums.p, 0, 2 * sizeof(unsigned long long), st));
-    HIPCHK(nldsc::launch_pack_table(e->l2.p, e->l2d.p, e->maf.p, e->rstd.p, e->ws3.p, M, lo, hi, e->split_width,
-                                    e->split_table, e->sums.p, st));
-    HIPCHK(hipMemcpyAsync(e->h_sums.p, e->sums.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    const auto t0 = Clock::now();
+    HIPCHK(nldsc::launch_import_acc(e->l2_acc.p, e->l2d_acc.p, e->ws_acc.p, e->split.M, e->split.own_lo, import_n,
+                                    reinterpret_cast<const long long*>(import_dev), e->stream));
+    HIPCHK(hipEventRecord(e->ev[4], e->stream));
+    double sw = 0, sd = 0;
+    const int rc = finish_table(e, &sw, &sd, err, errlen);
+    if (rc) return rc;
     HIPCHK(hipEventSynchronize(e->ev_issued));  // (h_sums[2]: the first call's issued-product count)
-    const unsigned long long* s = reinterpret_cast<const unsigned long long*>(e->h_sums.p);
-    const double sw = (double)s[0], sd = e->split_dom ? (double)s[1] : 0.0, N = (double)e->split_N;
     float f = 0;
     HIPCHK(hipEventElapsedTime(&f, e->ev[4], e->ev[5])); e->ms[4] = f;
-    const auto t1 = std::chrono::steady_clock::now();
     // (total: both calls' host time, without the exchange between them)
-    e->ms[5] = e->split_ms1 + std::chrono::duration<double, std::milli>(t1 - t0).count();
-    e->flop_issued = (double)s[2] * 2.0 * BLK * BLK * (double)e->split_row_bytes * 4.0;
-    e->pairs = sw;
-    e->flop_alg = 2.0 * N * (0.5 * sw + sd);
-    e->ops_alg_i8 = 2.0 * N * (2.0 * sw + 2.0 * sd);
+    e->ms[5] = e->split.ms1 + ms_between(t0, Clock::now());
+    record_metrics(e, sw, sd, e->split.N, e->split.row_bytes);
     return NLDSC_OK;
 }
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "band_plan.h"
+
 namespace nldsc {
 
 // Per-SNP constants of the exact-integer path: with x = additive count, h = [genotype >= 1],
@@ -99,45 +101,50 @@ hipError_t launch_plan(int n, int own_lo, int own_hi, const int* A, int* E, int*
                        hipStream_t st, bool pair = false, int4* small_items = nullptr);
 hipError_t launch_plan_emit(int n, const int2* rows, const int* meta, const int* offsets, int4* items, hipStream_t st,
                             bool pair = false);
-hipError_t launch_band(bool dom, int wps, int n_items, const uint32_t* geno, int pitch_words, int n_it,
-                       const float2* lut, const int4* items, const double* pos, const int* Lw, const int* Rw,
-                       const uint8_t* sflags, int n_snp, double ld_wind, double n_org, double rsq_thr, int own_lo,
-                       int own_hi, double* l2_acc, double* l2d_acc, int* ws_acc, hipStream_t st);
-hipError_t launch_band_i8(bool dom, int max_nc, int n_items, const uint32_t* geno, int pitch_words, int n_it,
-                          const SnpConst* cst, const int4* items, const double* pos, const int* Lw, const int* Rw,
-                          const uint8_t* sflags, int n_snp, double ld_wind, double n_org, double rsq_thr, int own_lo,
-                          int own_hi, double* l2_acc, double* l2d_acc, int* ws_acc, bool xcd, const uint8_t* blk_rep,
-                          int which, hipStream_t st);
-// K-loop chunks (128 samples each) per fp32 accumulation segment of the fp4 path: rows longer than this
-// (N > 2^19) run the segmented kernel, which folds the fp32 Gram into int32 after every segment
-constexpr int F4_SEG_CHUNKS = 4096;
+// What every band launch of a run shares, filled once per run (ld_engine.cpp fill_band_args): the resident rows, the
+// per-SNP inputs, the pair epilogue's thresholds and accumulators, the replay and routing context, the stream.  The
+// launchers spread it over the kernels' flat __restrict__ parameter lists.
+struct BandArgs {
+    const uint32_t* geno;  // resident rows: pitch_words 32-bit words each, n_it K-loop chunks
+    int pitch_words, n_it;
+    const SnpConst* cst;  // (exact paths)
+    const float2* lut;    // (fp32 path)
+    const double* pos;
+    const int *Lw, *Rw;
+    const uint8_t* sflags;
+    int n_snp;
+    double ld_wind, n_org, rsq_thr;
+    int own_lo, own_hi;  // SNPs whose sums accumulate
+    double *l2_acc, *l2d_acc;
+    int* ws_acc;
+    bool dom;
+    // per 32-SNP block, 1 if a SNP carries replayed fp32 vectors (ka / kr != 0), or nullptr (no replay): its items run
+    // in a second launch (the exact kernels' KC instantiation)
+    const uint8_t* blk_rep;
+    const int2* rows;  // the single-block plan's rows (nblk), read by the super-item kernels
+    int nblk, route_shift;  // (super-items of 2^route_shift blocks a side: read only beside a blk_miss)
+    hipStream_t st;
+};
+// rare-variant items deferred by launch_band_f4: their Gram tiles, block pairs and the slot counter
+struct DeferredEpi { float* gram; int4* items; int* count; };
+// `which` of the exact launchers: 1 the main launch (items of blocks without a replayed SNP), 2 the KC launch, 3 both.
+// blk_miss (or nullptr) is the routing map of this launch: super-item launches and single-block launches get different
+// ones, so it is not part of the bundle.
+hipError_t launch_band(const BandArgs& a, int wps, const int4* items, int n_items);
+hipError_t launch_band_i8(const BandArgs& a, const int4* items, int n_items, int which);
 // exact path on fp4 MFMAs (N < 2^27), items (I, J0, 1, 0) (max_nc 1), or for additive-only unsegmented rows also
-// (I, J0, 2, 0) column-block pairs (max_nc 2; blk_miss then drops routed column blocks per block).  blk_rep (or nullptr): per 32-SNP
-// block, 1 if a SNP carries replayed fp32 vectors (ka / kr != 0): its items run in a second launch (the exact
-// kernels' KC instantiation).  which: 1 the main launch (items of other blocks), 2 the KC launch, 3 both
-hipError_t launch_band_f4(bool dom, int max_nc, int n_items, const uint32_t* geno, int pitch_words, int n_it,
-                          const SnpConst* cst, const int4* items, const double* pos, const int* Lw, const int* Rw,
-                          const uint8_t* sflags, int n_snp, double ld_wind, double n_org, double rsq_thr, int own_lo,
-                          int own_hi, double* l2_acc, double* l2d_acc, int* ws_acc, bool xcd, const uint8_t* blk_rep,
-                          int which, hipStream_t st, const uint8_t* blk_miss = nullptr, int round_items = 0,
-                          int route_shift = 1, float* rep_gram = nullptr, int4* rep_items = nullptr, int* rep_count = nullptr);
-// rep_gram (unsegmented rows): the items holding a replayed rare variant run their K loops in the main launch and store
-// each block pair's exact Gram tiles (rep_gram slot = atomicAdd(rep_count), 8192 floats; rep_items[slot] = the block
-// pair); after the replay, launch_band_f4_deferred_epi runs their epilogues (max_items >= the slots used) in place of
+// (I, J0, 2, 0) column-block pairs (max_nc 2; blk_miss then drops routed column blocks per block)
+hipError_t launch_band_f4(const BandArgs& a, int max_nc, const int4* items, int n_items, int which,
+                          const uint8_t* blk_miss, int round_items, const DeferredEpi* rep);
+// rep (unsegmented rows; or nullptr): the items holding a replayed rare variant run their K loops in the main launch and
+// store each block pair's exact Gram tiles (gram slot = atomicAdd(count), 8192 floats; items[slot] = the block pair);
+// after the replay, launch_band_f4_deferred_epi runs their epilogues (max_items >= the slots used) in place of
 // the KC launch
-hipError_t launch_band_f4_deferred_epi(bool dom, int max_items, const SnpConst* cst, const int4* rep_items,
-                                      const int* rep_count, const float* rep_gram, const double* pos, const int* Lw,
-                                      const int* Rw, const uint8_t* sflags, int n_snp, double ld_wind, double n_org,
-                                      double rsq_thr, int own_lo, int own_hi, double* l2_acc, double* l2d_acc,
-                                      int* ws_acc, const uint8_t* blk_rep, hipStream_t st);
+hipError_t launch_band_f4_deferred_epi(const BandArgs& a, int max_items, const DeferredEpi& rep);
 // the same with the K loop split in P pieces (small launches: better filled wave slots): partial Gram tiles to
 // `gram` (n_items * P * 8192 floats), then an epilogue kernel (unsegmented rows, n_it <= F4_SEG_CHUNKS)
-hipError_t launch_band_f4_split(bool dom, int P, int n_items, const uint32_t* geno, int pitch_words, int n_it,
-                                const SnpConst* cst, const int4* items, const double* pos, const int* Lw, const int* Rw,
-                                const uint8_t* sflags, int n_snp, double ld_wind, double n_org, double rsq_thr,
-                                int own_lo, int own_hi, double* l2_acc, double* l2d_acc, int* ws_acc,
-                                const uint8_t* blk_rep, float* gram, int which, hipStream_t st,
-                                const uint8_t* blk_miss = nullptr, int route_shift = 1);
+hipError_t launch_band_f4_split(const BandArgs& a, int P, const int4* items, int n_items, float* gram, int which,
+                                const uint8_t* blk_miss);
 // 2 x 2 block-pair workgroups (unsegmented rows, gpu plan): super-items (I2, J2, 1, 0) over row / column
 // super-blocks of two 32-SNP blocks, planned from the single-block rows (launch_plan) by launch_plan_super (meta2
 // as meta; counts2 capacity ceil(nblk2/16)^2) and launch_plan_emit_super; the kernel reads `rows` (nblk) to skip the
@@ -151,21 +158,12 @@ int plan_super_counts(int n, int shift);
 hipError_t launch_plan_super(int n, const int2* rows, int2* rows2, int* counts2, int* meta2, int shift, hipStream_t st);
 hipError_t launch_plan_emit_super(int n, const int2* rows2, const int* meta2, const int* offsets2, int4* items2,
                                   int shift, hipStream_t st);
-hipError_t launch_band_f4_t2(bool dom, int n_items2, const uint32_t* geno, int pitch_words, int n_it,
-                             const SnpConst* cst, const int4* items2, const int2* rows, int nblk, const double* pos,
-                             const int* Lw, const int* Rw, const uint8_t* sflags, int n_snp, double ld_wind,
-                             double n_org, double rsq_thr, int own_lo, int own_hi, double* l2_acc, double* l2d_acc,
-                             int* ws_acc, bool xcd, const uint8_t* blk_rep, const uint8_t* blk_miss, int which,
-                             hipStream_t st);
+hipError_t launch_band_f4_t2(const BandArgs& a, const int4* items2, int n_items2, int which, const uint8_t* blk_miss);
 // 4 x 4 block-pair workgroups (the quad kernel: one wave per SIMD, 64 x 64 SNP tiles) for the missing-free 4 x 4
 // super-items (I4, J4, 1, 0) of launch_plan_super(shift 2); blk_miss required (route_shift 2 for the other kernels).
 constexpr int Q_STAGES = 4;
-hipError_t launch_band_f4_q(bool dom, int n_items4, const uint32_t* geno, int pitch_words, int n_it,
-                            const SnpConst* cst, const int4* items4, const int2* rows, int nblk, const double* pos,
-                            const int* Lw, const int* Rw, const uint8_t* sflags, int n_snp, double ld_wind,
-                            double n_org, double rsq_thr, int own_lo, int own_hi, double* l2_acc, double* l2d_acc,
-                            int* ws_acc, bool xcd, const uint8_t* blk_rep, const uint8_t* blk_miss, int which,
-                            hipStream_t st, int round_items = 0);
+hipError_t launch_band_f4_q(const BandArgs& a, const int4* items4, int n_items4, int which, const uint8_t* blk_miss,
+                            int round_items);
 // blk_miss[b] = block b holds a missing call (launch_block_missing_rows).  Passed to the fp4 kernels (unsegmented rows)
 // it routes the super-items: missing-free ones to a super-item kernel (operand-feed bound at 3 products per K step,
 // where sharing the strips pays), the block pairs of the others to the single-block kernel (MFMA bound at 8 products)

@@ -3071,33 +3071,30 @@ hipError_t launch_plan_emit(int n, const int2* rows, const int* meta, const int*
     return hipGetLastError();
 }
 
-hipError_t launch_band(bool dom, int wps, int n_items, const uint32_t* geno, int pitch_words, int n_it,
-                       const float2* lut, const int4* items, const double* pos, const int* Lw, const int* Rw,
-                       const uint8_t* sflags, int n_snp, double ld_wind, double n_org, double rsq_thr, int own_lo,
-                       int own_hi, double* l2_acc, double* l2d_acc, int* ws_acc, hipStream_t st) {
+// A run's shared band arguments (BandArgs a) in the order the band kernels' flat parameter lists take them: the
+// resident rows, the per-SNP inputs, the pair epilogue's thresholds and accumulators.  Every band kernel is launched
+// with the XCD remap on (the 1 after A_EPI).
+#define A_ROWS a.geno, a.pitch_words, a.n_it
+#define A_SNPS a.pos, a.Lw, a.Rw, a.sflags, a.n_snp
+#define A_EPI a.ld_wind, a.n_org, a.rsq_thr, a.own_lo, a.own_hi, a.l2_acc, a.l2d_acc, a.ws_acc
+
+hipError_t launch_band(const BandArgs& a, int wps, const int4* items, int n_items) {
     if (n_items <= 0) return hipSuccess;
 #define NLDSC_BAND(DOM_, WPS_)                                                                                       \
-    hipLaunchKernelGGL((band_kernel<DOM_, WPS_>), dim3(n_items), dim3(64), 0, st, geno, pitch_words, n_it, lut, items, \
-                       pos, Lw, Rw, sflags, n_snp, ld_wind, n_org, rsq_thr, own_lo, own_hi, l2_acc, l2d_acc, ws_acc)
-    if (dom) { if (wps == 2) NLDSC_BAND(true, 2); else NLDSC_BAND(true, 1); }
+    hipLaunchKernelGGL((band_kernel<DOM_, WPS_>), dim3(n_items), dim3(64), 0, a.st, A_ROWS, a.lut, items, A_SNPS, A_EPI)
+    if (a.dom) { if (wps == 2) NLDSC_BAND(true, 2); else NLDSC_BAND(true, 1); }
     else { if (wps == 2) NLDSC_BAND(false, 2); else NLDSC_BAND(false, 1); }
 #undef NLDSC_BAND
     return hipGetLastError();
 }
 
-hipError_t launch_band_i8(bool dom, int max_nc, int n_items, const uint32_t* geno, int pitch_words, int n_it,
-                          const SnpConst* cst, const int4* items, const double* pos, const int* Lw, const int* Rw,
-                          const uint8_t* sflags, int n_snp, double ld_wind, double n_org, double rsq_thr, int own_lo,
-                          int own_hi, double* l2_acc, double* l2d_acc, int* ws_acc, bool xcd, const uint8_t* blk_rep,
-                          int which, hipStream_t st) {
+hipError_t launch_band_i8(const BandArgs& a, const int4* items, int n_items, int which) {
     if (n_items <= 0) return hipSuccess;
-    if (max_nc != 1) return hipErrorInvalidValue;  // single block-pair items
 #define NLDSC_BAND(DOM_, KC_)                                                                                       \
-    hipLaunchKernelGGL((band_i8_kernel<DOM_, KC_>), dim3(n_items), dim3(64), 0, st, geno, pitch_words, n_it, cst,    \
-                       items, pos, Lw, Rw, sflags, n_snp, ld_wind, n_org, rsq_thr, own_lo, own_hi, l2_acc, l2d_acc, \
-                       ws_acc, xcd ? 1 : 0, blk_rep)
-    if (which & 1) { if (dom) NLDSC_BAND(true, false); else NLDSC_BAND(false, false); }
-    if (blk_rep && (which & 2)) { if (dom) NLDSC_BAND(true, true); else NLDSC_BAND(false, true); }
+    hipLaunchKernelGGL((band_i8_kernel<DOM_, KC_>), dim3(n_items), dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS, \
+                       A_EPI, 1, a.blk_rep)
+    if (which & 1) { if (a.dom) NLDSC_BAND(true, false); else NLDSC_BAND(false, false); }
+    if (a.blk_rep && (which & 2)) { if (a.dom) NLDSC_BAND(true, true); else NLDSC_BAND(false, true); }
 #undef NLDSC_BAND
     return hipGetLastError();
 }
@@ -3136,131 +3133,108 @@ hipError_t launch_plan_emit_super(int n, const int2* rows2, const int* meta2, co
     return hipGetLastError();
 }
 
-hipError_t launch_band_f4_t2(bool dom, int n_items2, const uint32_t* geno, int pitch_words, int n_it,
-                             const SnpConst* cst, const int4* items2, const int2* rows, int nblk, const double* pos,
-                             const int* Lw, const int* Rw, const uint8_t* sflags, int n_snp, double ld_wind,
-                             double n_org, double rsq_thr, int own_lo, int own_hi, double* l2_acc, double* l2d_acc,
-                             int* ws_acc, bool xcd, const uint8_t* blk_rep, const uint8_t* blk_miss, int which,
-                             hipStream_t st) {
+hipError_t launch_band_f4_t2(const BandArgs& a, const int4* items2, int n_items2, int which, const uint8_t* blk_miss) {
     if (n_items2 <= 0) return hipSuccess;
-    if (n_it > F4_SEG_CHUNKS || n_it < 2 || (n_it & 1)) return hipErrorInvalidValue;
+    if (a.n_it > F4_SEG_CHUNKS || a.n_it < 2 || (a.n_it & 1)) return hipErrorInvalidValue;
 #define NLDSC_BAND(DOM_, KC_)                                                                                       \
-    hipLaunchKernelGGL((band_f4_t2_kernel<DOM_, T2_STAGES, KC_>), dim3(n_items2), dim3(256), 0, st, geno,           \
-                       pitch_words, n_it, cst, items2, rows, nblk, pos, Lw, Rw, sflags, n_snp, ld_wind, n_org,      \
-                       rsq_thr, own_lo, own_hi, l2_acc, l2d_acc, ws_acc, xcd ? 1 : 0, blk_rep, blk_miss)
-    if (which & 1) { if (dom) NLDSC_BAND(true, false); else NLDSC_BAND(false, false); }
-    if (blk_rep && (which & 2)) { if (dom) NLDSC_BAND(true, true); else NLDSC_BAND(false, true); }
+    hipLaunchKernelGGL((band_f4_t2_kernel<DOM_, T2_STAGES, KC_>), dim3(n_items2), dim3(256), 0, a.st, A_ROWS, a.cst, \
+                       items2, a.rows, a.nblk, A_SNPS, A_EPI, 1, a.blk_rep, blk_miss)
+    if (which & 1) { if (a.dom) NLDSC_BAND(true, false); else NLDSC_BAND(false, false); }
+    if (a.blk_rep && (which & 2)) { if (a.dom) NLDSC_BAND(true, true); else NLDSC_BAND(false, true); }
 #undef NLDSC_BAND
     return hipGetLastError();
 }
 
-hipError_t launch_band_f4_q(bool dom, int n_items4, const uint32_t* geno, int pitch_words, int n_it,
-                            const SnpConst* cst, const int4* items4, const int2* rows, int nblk, const double* pos,
-                            const int* Lw, const int* Rw, const uint8_t* sflags, int n_snp, double ld_wind,
-                            double n_org, double rsq_thr, int own_lo, int own_hi, double* l2_acc, double* l2d_acc,
-                            int* ws_acc, bool xcd, const uint8_t* blk_rep, const uint8_t* blk_miss, int which,
-                            hipStream_t st, int round_items) {
+hipError_t launch_band_f4_q(const BandArgs& a, const int4* items4, int n_items4, int which, const uint8_t* blk_miss,
+                            int round_items) {
     if (n_items4 <= 0) return hipSuccess;
-    if (n_it > F4_SEG_CHUNKS || n_it < 2 || (n_it & 1) || blk_miss == nullptr) return hipErrorInvalidValue;
+    if (a.n_it > F4_SEG_CHUNKS || a.n_it < 2 || (a.n_it & 1) || blk_miss == nullptr) return hipErrorInvalidValue;
     // round_items > 0: launches of that many super-items (one workgroup per CU each), so the workgroups on an XCD
     // start together and stream their shared strips at nearby K offsets (not the KC launch)
     int chunk = round_items > 0 ? round_items : n_items4;
 #define NLDSC_BAND(DOM_, KC_)                                                                                       \
     for (int o = 0; o < n_items4; o += chunk)                                                                        \
     hipLaunchKernelGGL((band_f4_q_kernel<DOM_, Q_STAGES, KC_>), dim3(std::min(chunk, n_items4 - o)), dim3(256),     \
-                       0, st, geno, pitch_words, n_it, cst, items4 + o, rows, nblk, pos, Lw, Rw, sflags, n_snp,     \
-                       ld_wind, n_org, rsq_thr, own_lo, own_hi, l2_acc, l2d_acc, ws_acc, xcd ? 1 : 0, blk_rep, blk_miss)
+                       0, a.st, A_ROWS, a.cst, items4 + o, a.rows, a.nblk, A_SNPS, A_EPI, 1, a.blk_rep, blk_miss)
     if (which & 1) {
-        if (dom) NLDSC_BAND(true, false);
+        if (a.dom) NLDSC_BAND(true, false);
         else NLDSC_BAND(false, false);
     }
     chunk = n_items4;
-    if (blk_rep && (which & 2)) {
-        if (dom) NLDSC_BAND(true, true);
+    if (a.blk_rep && (which & 2)) {
+        if (a.dom) NLDSC_BAND(true, true);
         else NLDSC_BAND(false, true);
     }
 #undef NLDSC_BAND
     return hipGetLastError();
 }
 
-hipError_t launch_band_f4_split(bool dom, int P, int n_items, const uint32_t* geno, int pitch_words, int n_it,
-                                const SnpConst* cst, const int4* items, const double* pos, const int* Lw, const int* Rw,
-                                const uint8_t* sflags, int n_snp, double ld_wind, double n_org, double rsq_thr,
-                                int own_lo, int own_hi, double* l2_acc, double* l2d_acc, int* ws_acc,
-                                const uint8_t* blk_rep, float* gram, int which, hipStream_t st,
-                                const uint8_t* blk_miss, int route_shift) {
+hipError_t launch_band_f4_split(const BandArgs& a, int P, const int4* items, int n_items, float* gram, int which,
+                                const uint8_t* blk_miss) {
     if (n_items <= 0) return hipSuccess;
-    if (n_it > F4_SEG_CHUNKS || P < 1 || 2 * P > n_it) return hipErrorInvalidValue;
+    if (a.n_it > F4_SEG_CHUNKS || P < 1 || 2 * P > a.n_it) return hipErrorInvalidValue;
     const dim3 grid_p((unsigned)n_items * (unsigned)P);
     if (!(which & 1)) goto kc;  // the partial tiles of every item come from the main launch
-    if (dom) hipLaunchKernelGGL((band_f4_part_kernel<true>), grid_p, dim3(64), 0, st, geno, pitch_words, n_it, cst,
-                                items, pos, Lw, Rw, sflags, n_snp, P, gram, blk_miss, route_shift);
-    else hipLaunchKernelGGL((band_f4_part_kernel<false>), grid_p, dim3(64), 0, st, geno, pitch_words, n_it, cst,
-                            items, pos, Lw, Rw, sflags, n_snp, P, gram, blk_miss, route_shift);
+    if (a.dom) hipLaunchKernelGGL((band_f4_part_kernel<true>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS,
+                                  P, gram, blk_miss, a.route_shift);
+    else hipLaunchKernelGGL((band_f4_part_kernel<false>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS, P,
+                            gram, blk_miss, a.route_shift);
 #define NLDSC_EPI(DOM_, KC_)                                                                                        \
-    hipLaunchKernelGGL((band_f4_epi_kernel<DOM_, KC_>), dim3(n_items), dim3(64), 0, st, cst, items, pos, Lw, Rw,    \
-                       sflags, n_snp, ld_wind, n_org, rsq_thr, own_lo, own_hi, l2_acc, l2d_acc, ws_acc, blk_rep, P, gram, \
-                       blk_miss, route_shift, nullptr)
-    if (dom) NLDSC_EPI(true, false); else NLDSC_EPI(false, false);
+    hipLaunchKernelGGL((band_f4_epi_kernel<DOM_, KC_>), dim3(n_items), dim3(64), 0, a.st, a.cst, items, A_SNPS,     \
+                       A_EPI, a.blk_rep, P, gram, blk_miss, a.route_shift, nullptr)
+    if (a.dom) NLDSC_EPI(true, false); else NLDSC_EPI(false, false);
 kc:
-    if (blk_rep && (which & 2)) { if (dom) NLDSC_EPI(true, true); else NLDSC_EPI(false, true); }
+    if (a.blk_rep && (which & 2)) { if (a.dom) NLDSC_EPI(true, true); else NLDSC_EPI(false, true); }
 #undef NLDSC_EPI
     return hipGetLastError();
 }
 
-hipError_t launch_band_f4_deferred_epi(bool dom, int max_items, const SnpConst* cst, const int4* rep_items,
-                                      const int* rep_count, const float* rep_gram, const double* pos, const int* Lw,
-                                      const int* Rw, const uint8_t* sflags, int n_snp, double ld_wind, double n_org,
-                                      double rsq_thr, int own_lo, int own_hi, double* l2_acc, double* l2d_acc,
-                                      int* ws_acc, const uint8_t* blk_rep, hipStream_t st) {
+hipError_t launch_band_f4_deferred_epi(const BandArgs& a, int max_items, const DeferredEpi& rep) {
     if (max_items <= 0) return hipSuccess;
-    if (dom)
-        hipLaunchKernelGGL((band_f4_epi_kernel<true, true>), dim3(max_items), dim3(64), 0, st, cst, rep_items, pos, Lw,
-                           Rw, sflags, n_snp, ld_wind, n_org, rsq_thr, own_lo, own_hi, l2_acc, l2d_acc, ws_acc, blk_rep,
-                           1, rep_gram, nullptr, 1, rep_count);
+    if (a.dom)
+        hipLaunchKernelGGL((band_f4_epi_kernel<true, true>), dim3(max_items), dim3(64), 0, a.st, a.cst, rep.items,
+                           A_SNPS, A_EPI, a.blk_rep, 1, rep.gram, nullptr, 1, rep.count);
     else
-        hipLaunchKernelGGL((band_f4_epi_kernel<false, true>), dim3(max_items), dim3(64), 0, st, cst, rep_items, pos,
-                           Lw, Rw, sflags, n_snp, ld_wind, n_org, rsq_thr, own_lo, own_hi, l2_acc, l2d_acc, ws_acc,
-                           blk_rep, 1, rep_gram, nullptr, 1, rep_count);
+        hipLaunchKernelGGL((band_f4_epi_kernel<false, true>), dim3(max_items), dim3(64), 0, a.st, a.cst, rep.items,
+                           A_SNPS, A_EPI, a.blk_rep, 1, rep.gram, nullptr, 1, rep.count);
     return hipGetLastError();
 }
 
-hipError_t launch_band_f4(bool dom, int max_nc, int n_items, const uint32_t* geno, int pitch_words, int n_it,
-                          const SnpConst* cst, const int4* items, const double* pos, const int* Lw, const int* Rw,
-                          const uint8_t* sflags, int n_snp, double ld_wind, double n_org, double rsq_thr, int own_lo,
-                          int own_hi, double* l2_acc, double* l2d_acc, int* ws_acc, bool xcd, const uint8_t* blk_rep,
-                          int which, hipStream_t st, const uint8_t* blk_miss, int round_items, int route_shift,
-                          float* rep_gram, int4* rep_items, int* rep_count) {
+hipError_t launch_band_f4(const BandArgs& a, int max_nc, const int4* items, int n_items, int which,
+                          const uint8_t* blk_miss, int round_items, const DeferredEpi* rep) {
     if (n_items <= 0) return hipSuccess;
     // single block-pair items, or (additive-only, unsegmented rows) column-block pairs
-    if (max_nc != 1 && !(max_nc == 2 && !dom && n_it <= F4_SEG_CHUNKS)) return hipErrorInvalidValue;
-    if (blk_miss != nullptr && n_it > F4_SEG_CHUNKS) return hipErrorInvalidValue;  // routing: unsegmented rows only
+    if (max_nc != 1 && !(max_nc == 2 && !a.dom && a.n_it <= F4_SEG_CHUNKS)) return hipErrorInvalidValue;
+    if (blk_miss != nullptr && a.n_it > F4_SEG_CHUNKS) return hipErrorInvalidValue;  // routing: unsegmented rows only
+    const DeferredEpi none = {nullptr, nullptr, nullptr};
+    const DeferredEpi& d = rep ? *rep : none;
     // round_items > 0: the items go in launches of that many (one round of the wave slots each), see ld_engine.cpp;
     // not the KC launch (items holding a replayed rare variant: few, the others return at once)
     int chunk = round_items > 0 ? round_items : n_items;
 #define NLDSC_BAND_NC(DOM_, WPS_, SEG_, KC_, NCX_)                                                                  \
     for (int o = 0; o < n_items; o += chunk)                                                                      \
     hipLaunchKernelGGL((band_f4_kernel<DOM_, WPS_, SEG_, KC_, NCX_>), dim3(std::min(chunk, n_items - o)), dim3(64), 0, \
-                       st, geno, pitch_words,                                                                         \
-                       n_it, cst, items + o, pos, Lw, Rw, sflags, n_snp, ld_wind, n_org, rsq_thr, own_lo, own_hi,       \
-                       l2_acc, l2d_acc, ws_acc, xcd ? 1 : 0, blk_rep, blk_miss, route_shift, SEG_ ? nullptr : rep_gram, \
-                       rep_items, rep_count)
+                       a.st, A_ROWS, a.cst, items + o, A_SNPS, A_EPI, 1, a.blk_rep, blk_miss, a.route_shift,        \
+                       SEG_ ? nullptr : d.gram, d.items, d.count)
 #define NLDSC_BAND(DOM_, WPS_, SEG_, KC_) NLDSC_BAND_NC(DOM_, WPS_, SEG_, KC_, 1)
 #define NLDSC_PICK(KC_)                                                                                              \
-    if (n_it > F4_SEG_CHUNKS) { if (dom) NLDSC_BAND(true, 1, F4_SEG_CHUNKS, KC_); else NLDSC_BAND(false, 2, F4_SEG_CHUNKS, KC_); } \
-    else if (dom) NLDSC_BAND(true, 2, 0, KC_);                                                                       \
+    if (a.n_it > F4_SEG_CHUNKS) { if (a.dom) NLDSC_BAND(true, 1, F4_SEG_CHUNKS, KC_); else NLDSC_BAND(false, 2, F4_SEG_CHUNKS, KC_); } \
+    else if (a.dom) NLDSC_BAND(true, 2, 0, KC_);                                                                     \
     else if (max_nc == 2) NLDSC_BAND_NC(false, 2, 0, KC_, 2);                                                        \
     else NLDSC_BAND(false, 2, 0, KC_)
     // segmented kernel: the add+dom variant needs more than 256 registers (2 waves / SIMD would spill)
     if (which & 1) { NLDSC_PICK(false); }
     chunk = n_items;
-    // (with rep_gram the KC items ran their K loops in the main launch: launch_band_f4_deferred_epi after the replay)
-    if (blk_rep && (which & 2) && (rep_gram == nullptr || n_it > F4_SEG_CHUNKS)) { NLDSC_PICK(true); }
+    // (with rep the KC items ran their K loops in the main launch: launch_band_f4_deferred_epi after the replay)
+    if (a.blk_rep && (which & 2) && (d.gram == nullptr || a.n_it > F4_SEG_CHUNKS)) { NLDSC_PICK(true); }
 #undef NLDSC_PICK
 #undef NLDSC_BAND
 #undef NLDSC_BAND_NC
     return hipGetLastError();
 }
+#undef A_ROWS
+#undef A_SNPS
+#undef A_EPI
 
 hipError_t launch_finalize(const int* Lw, const double* l2_acc, const double* l2d_acc, const int* ws_acc, int n_snp,
                            int own_lo, int own_hi, bool dom, double* l2, double* l2d, int* ws3, hipStream_t st) {

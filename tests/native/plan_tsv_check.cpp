@@ -4,6 +4,8 @@
 //    negative, NaN and unsorted positions, MAF failures, empty and partial owned ranges, windows from 0 to
 //    everything — checked against a brute-force restatement of the reference's ChunkwiseReader pointers
 //    (stream.h:131-155,182-197): every needed 32-SNP block pair covered exactly once, every item in range.
+//  * launch shaping (band_plan.cpp choose_ksplit, choose_band, shape_single, band_kernel_code): a table of cost-model
+//    values and the structural rules the GPU tests rely on.
 //  * nldsc_format_scores (tsv_format.cpp): "%.5f" fields, NaN as '', against snprintf on random, tie,
 //    tiny, huge and non-finite values.
 #include <cmath>
@@ -177,10 +179,75 @@ static void check_sorted(std::mt19937_64& rng, int iter) {
     CHECK(nldsc::positions_nonneg_sorted(P.data(), M) == expect, "positions_nonneg_sorted (M=%d, iter %d)", M, iter);
 }
 
+// Launch shaping (band_plan.h).  The choose_ksplit values are those of the cost-model lambda this function replaced
+// in ld_engine.cpp, compiled on its own and run over these inputs (g++ -O2 and clang++ -O3 agree) — not values read
+// back from the new function.
+static void check_launch_shape(std::mt19937_64& rng) {
+    using namespace nldsc;
+    static const int table[][4] = {  // n_items, n_it, n_cu, P
+        {1458, 2466, 256, 4},  {3283, 2466, 256, 3}, {13000, 2466, 256, 1}, {26034, 2466, 256, 1},
+        {2048, 2466, 256, 1},  {2049, 2466, 256, 4}, {1, 2466, 256, 8},     {300, 1564, 256, 6},
+        {700, 1025, 256, 5},   {100, 2, 256, 1},     {100, 4, 256, 1},      {20000, 4097, 256, 1},
+        {0, 2466, 256, 1},     {1000, 4096, 256, 2}, {1500, 2466, 304, 3},  {500, 512, 64, 1},
+        {40, 16, 8, 3},        {2000, 3000, 128, 1}, {12000, 4096, 256, 1}, {5, 5, 256, 2},
+        {3, 6, 1, 2},          {1024, 1024, 256, 2}};
+    for (const auto& t : table) {
+        CHECK(choose_ksplit(t[0], t[1], t[2], true) == t[3], "choose_ksplit(%d, %d, %d) = %d, expected %d", t[0], t[1],
+              t[2], choose_ksplit(t[0], t[1], t[2], true), t[3]);
+        CHECK(choose_ksplit(t[0], t[1], t[2], false) == 1, "choose_ksplit(%d, %d, %d) disabled", t[0], t[1], t[2]);
+    }
+    const int n_its[] = {2, 512, 1023, 1024, 1564, 2466, F4_SEG_CHUNKS, F4_SEG_CHUNKS + 1, 8192};
+    const int n_cus[] = {1, 8, 64, 256, 304};
+    for (int iter = 0; iter < 20000; ++iter) {
+        const int n_it = n_its[rng() % 9], n_cu = n_cus[rng() % 5], slots = 8 * n_cu;
+        const int edge[] = {0, 1, slots - 1, slots, slots + 1, 2 * slots, 3 * slots + slots / 2};
+        const int n = rng() % 2 ? edge[rng() % 7] : (int)(rng() % (size_t)(14 * slots));
+        const bool use_f4 = rng() % 8 != 0, rounds = rng() % 4 != 0, nc2 = rng() % 4 == 0, ok = rng() % 4 != 0;
+        const bool want = rng() % 4 != 0, t2_cand = rng() % 2 != 0;
+        const size_t max_slots = rng() % 2 ? (size_t)1 << 16 : (size_t)(rng() % (size_t)(4 * slots));
+        const bool round_cond = use_f4 && rounds && n_it >= 1024 && n_it <= F4_SEG_CHUNKS && n >= slots;
+        // the whole band: K-split overridden to 1 under the round-launch condition, super-items only without either
+        const bool en = use_f4 && !nc2 && ok;
+        const int p_whole = choose_ksplit(n, n_it, n_cu, en);
+        const BandChoice c = choose_band(n, n_it, n_cu, use_f4, en, rounds, t2_cand);
+        CHECK(c.ksplit == (round_cond ? 1 : p_whole), "band K-split %d (model %d, rounds %d)", c.ksplit, p_whole,
+              (int)round_cond);
+        CHECK(c.use_t2 == (t2_cand && n > 0 && p_whole == 1), "use_t2 %d (n %d, model %d)", (int)c.use_t2, n, p_whole);
+        // the single-block launches
+        const int ksplit = rng() % 4 ? 1 : 1 + (int)(rng() % 8);
+        const SingleShape s = shape_single(n, n_it, n_cu, use_f4, ksplit, rounds, nc2, ok, want, max_slots);
+        CHECK(s.round_items == (round_cond && ksplit == 1 ? slots : 0), "round_items %d (n %d, n_it %d, n_cu %d)",
+              s.round_items, n, n_it, n_cu);
+        const int tail = n - s.n_full;
+        CHECK(s.n_full >= 0 && tail >= 0 && s.tail_p >= 1 && s.tail_p <= 8, "shape (%d, %d, %d)", s.n_full, tail, s.tail_p);
+        if (s.tail_p > 1) {
+            CHECK(s.round_items > 0 && s.n_full % s.round_items == 0 && tail > 0 && tail < s.round_items,
+                  "K-split tail of %d after %d items in rounds of %d", tail, s.n_full, s.round_items);
+            CHECK(s.tail_p == choose_ksplit(tail, n_it, n_cu, en) && 2 * s.tail_p <= n_it, "tail_p %d", s.tail_p);
+        } else {
+            CHECK(tail == 0, "%d items in no launch", tail);
+        }
+        const bool fits = (size_t)s.n_full * (nc2 ? 2 : 1) <= max_slots;
+        CHECK(s.defer == (want && use_f4 && ksplit == 1 && n_it <= F4_SEG_CHUNKS && fits), "defer %d (n_full %d of %zu)",
+              (int)s.defer, s.n_full, max_slots);
+    }
+    // the C3 tail: 1 458 items past 12 full rounds, K-split in 4
+    const SingleShape c3 = shape_single(26034, 2466, 256, true, 1, true, false, true, true, (size_t)1 << 16);
+    CHECK(c3.round_items == 2048 && c3.n_full == 24576 && c3.tail_p == 4 && c3.defer, "C3 shape (%d, %d, %d, %d)",
+          c3.round_items, c3.n_full, c3.tail_p, (int)c3.defer);
+    CHECK(band_kernel_code(true, 3, 2, 1, 2466) == NLDSC_BAND_F4_QUAD && band_kernel_code(true, 1, 2, 1, 2466) == NLDSC_BAND_F4_ROUTED &&
+              band_kernel_code(true, 2, 2, 1, 2466) == NLDSC_BAND_F4_2X2 && band_kernel_code(false, 3, 2, 1, 2466) == NLDSC_BAND_F4 &&
+              band_kernel_code(false, 3, 2, 3, 2466) == NLDSC_BAND_F4_KSPLIT && band_kernel_code(false, 3, 2, 1, 4097) == NLDSC_BAND_F4_SEG &&
+              band_kernel_code(false, 3, 1, 1, 2466) == NLDSC_BAND_I8 && band_kernel_code(false, 3, 0, 1, 2466) == NLDSC_BAND_F32,
+          "band kernel codes");
+}
+
 int main() {
     std::mt19937_64 rng(2024);
     for (int it = 0; it < 600; ++it) check_plan(rng, it);
     for (int it = 0; it < 2000; ++it) check_sorted(rng, it);
+    std::mt19937_64 shape_rng(2025);  // (its own stream: the table checks below keep theirs)
+    check_launch_shape(shape_rng);
     // argument checks of the C ABI
     double p1[2] = {0, 1};
     uint8_t f1[2] = {1, 1};
