@@ -78,6 +78,11 @@ typedef struct nldsc_ld_result { /* LDScoreResult (data.h:21-31); n_snp elements
 
 /* One-shot call: read `p->bedfile`, compute on the GPU, fill `r`. */
 int nldsc_ld_calculate(const nldsc_ld_params* p, nldsc_ld_result* r, char* err, size_t errlen);
+/* The same on a subset of the individuals (PLINK's / LDSC's --keep): idx[n_keep] are the kept individuals' 0-based
+ * .fam line numbers, strictly ascending (nldsc_engine_set_keep below: the rules and the sample order); p->n_org is
+ * the file's individual count.  idx == NULL: everyone, as nldsc_ld_calculate. */
+int nldsc_ld_calculate_keep(const nldsc_ld_params* p, const int32_t* idx, int32_t n_keep, nldsc_ld_result* r,
+                            char* err, size_t errlen);
 
 /* Library / device information. */
 const char* nldsc_version(void);
@@ -123,6 +128,27 @@ int nldsc_engine_load_bed_host(nldsc_engine* e, const uint8_t* bed, size_t len, 
                                int32_t n_org, char* err, size_t errlen);
 int nldsc_engine_load_bed_device(nldsc_engine* e, const void* bed, size_t len, int32_t n_snp,
                                  int32_t n_org, char* err, size_t errlen);
+
+/* LD scores on a subset of the individuals (a reference panel inside a larger .bed: one ancestry group, unrelated,
+ * QC-passed samples; PLINK's / LDSC's --keep).  The next loads (all four) keep only the individuals idx[0 .. n_keep):
+ * 0-based .fam line numbers, strictly ascending, of a file of n_org_file individuals; the list is copied to the
+ * device.  idx == NULL clears the list.  With a list: NLDSC_E_ARG unless 1 <= n_keep <= n_org_file and every entry
+ * lies in [0, n_org_file) above the entry before it.  An image already resident is not affected.
+ *   - An individual's identity is PLINK's: .fam line s is bit pair s % 4, low pairs first (bits 2(s%4)+1 : 2(s%4)), of
+ *     byte s / 4 of every row, whatever sample order a run uses.
+ *   - With a list set the loaders take n_org = n_org_file (another n_org: NLDSC_E_ARG) and run their magic / size
+ *     checks against it; each slice of rows is compacted on the GPU to the .bed rows `plink --keep` would write (kept
+ *     individual k at pair k % 4 of byte k / 4, the last byte's unused pairs 00) and loaded as an image of n_keep
+ *     individuals.  Afterwards runs pass n_org = n_keep.
+ *   - Runs on such an image always use PLINK's sample order, as if NLDSC_FLAG_STRICT_PLINK_ORDER were set: the
+ *     reference's order would read the compact last byte's padding pairs as people at n_keep % 4 != 0, and the
+ *     reference has no --keep to mirror.
+ *   - A keep-load followed by a run equals, bit for bit in all seven result arrays, a plain load of the physically
+ *     subsetted .bed run with NLDSC_FLAG_STRICT_PLINK_ORDER, in every band mode and with every engine option. */
+int nldsc_engine_set_keep(nldsc_engine* e, const int32_t* idx, int32_t n_keep, int32_t n_org_file, char* err,
+                          size_t errlen);
+/* n_keep of the resident image when it was loaded with a keep list, 0 for a plain image. */
+int nldsc_engine_kept(const nldsc_engine* e);
 
 /* Compute LD scores for the SNPs with index in [own_begin, own_end) (position sharding:
  * each GPU owns a contiguous SNP range and recomputes the pairs it shares with its

@@ -51,13 +51,17 @@ def main():
               default=False)
 @click.option("--strict-plink-order", help="Use PLINK sample order in the last .bed byte (the reference does not)",
               is_flag=True, default=False)
+@click.option("--keep", help="Use only the individuals listed in FILE (FID IID per line), as PLINK's --keep; "
+                             "implies PLINK sample order (--strict-plink-order)", metavar="FILE", default=None)
+@click.option("--remove", help="Leave out the individuals listed in FILE (FID IID per line), as PLINK's --remove; "
+                               "implies PLINK sample order (--strict-plink-order)", metavar="FILE", default=None)
 @click.option("--additive-only", help="Skip the dominance terms (L2D = NaN)", is_flag=True, default=False)
 @click.option("--device", help="HIP device ordinal", type=int, default=None)
 @click.option("--quiet", help="No progress lines on stderr", is_flag=True, default=False)
 @click.option("--display", help="Display traceback", is_flag=True, default=False)
 @handle_exception
 def est_ld(bfile, out, ld_wind_kb, ld_wind_cm, maf_thr, std_thr, rsq_thr, extra, write_m, strict_plink_order,
-           additive_only, device, quiet):
+           keep, remove, additive_only, device, quiet):
     if sum(map(bool, [ld_wind_kb, ld_wind_cm])) != 1:
         raise RuntimeError("Please, specify exactly one --ld-wind option")
     elif ld_wind_kb:
@@ -71,11 +75,11 @@ def est_ld(bfile, out, ld_wind_kb, ld_wind_cm, maf_thr, std_thr, rsq_thr, extra,
         from .ldscore.genome import estimate_lds_genome
         estimate_lds_genome(bfile, ld_wind=ld_wind, wind_metric=wind_metric, maf_thr=maf_thr, std_thr=std_thr,
                             rsq_thr=rsq_thr, out=out, extra=extra, write_m=write_m, flags=flags, device=device,
-                            progress=not quiet)
+                            progress=not quiet, keep=keep, remove=remove)
         return
     estimate_lds(bfile, ld_wind=ld_wind, wind_metric=wind_metric, maf_thr=maf_thr, std_thr=std_thr,
                  rsq_thr=rsq_thr, out=out, extra=extra, summary=True, write_m=write_m, flags=flags, device=device,
-                 progress=not quiet)
+                 progress=not quiet, keep=keep, remove=remove)
 
 
 @main.command("h2", help="(not part of this engine) heritability estimation")

@@ -33,7 +33,7 @@ EXPORTED = (
     "nldsc_format_scores", "nldsc_engine_ksplit", "nldsc_engine_band_kernel", "nldsc_engine_band_round_items",
     "nldsc_engine_band_tail_ksplit", "nldsc_engine_run_device", "nldsc_engine_run_device_split",
     "nldsc_engine_run_device_finish", "nldsc_engine_set_option", "nldsc_host_alloc", "nldsc_host_free",
-    "nldsc_engine_result_direct",
+    "nldsc_engine_result_direct", "nldsc_engine_set_keep", "nldsc_engine_kept", "nldsc_ld_calculate_keep",
 )
 
 
@@ -126,6 +126,11 @@ def lib(path: str | None = None) -> ctypes.CDLL:
             L.nldsc_host_alloc.argtypes = [ctypes.c_size_t]
             L.nldsc_host_free.restype = None
             L.nldsc_host_free.argtypes = [vp]
+        if hasattr(L, "nldsc_engine_set_keep"):
+            L.nldsc_engine_set_keep.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32] + c_err
+            L.nldsc_engine_kept.argtypes = [vp]
+            L.nldsc_ld_calculate_keep.argtypes = [ctypes.POINTER(Params), vp, ctypes.c_int32,
+                                                  ctypes.POINTER(Result)] + c_err
         L.nldsc_synth_bed_device.argtypes = [ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float,
                                              ctypes.c_uint64] + c_err

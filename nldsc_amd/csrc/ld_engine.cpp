@@ -281,6 +281,11 @@ struct nldsc_engine {
     bool orient = true;     // store rows minor-homozygote-as-00 at load (option "orient" 0: file coding)
     bool oriented = false;  // the resident image was oriented
     int32_t n_snp = 0, n_org = 0;
+    // loads on a subset of the individuals (nldsc_engine_set_keep): the kept samples' .fam line numbers on the device,
+    // their count and the file's individual count for the next loads; `kept`: the resident image holds that many kept
+    // samples of a larger file (0: a plain image) — its runs use PLINK's sample order
+    DevBuf<int32_t> keep_idx;
+    int32_t keep_n = 0, keep_n_file = 0, kept = 0;
     // work buffers
 
     DevBuf<int> counts, cparts, Lw, Rw, Aw, ws_acc;  // (cparts: the count kernel's per-part counts)
@@ -429,6 +434,7 @@ int use_device(int32_t device, int* resolved, char* err, size_t errlen) {
 // device buffers of a resident image of n_snp rows (all rows, pitch padding, saved last bytes, per-row flags)
 hipError_t alloc_image(nldsc_engine* e, int32_t n_snp, int32_t n_org) {
     e->n_snp = e->n_org = 0;  // no valid image until finish_image
+    e->kept = 0;
     e->oriented = e->orient;  // (the load's slices all use the orientation rule in force when it starts)
     hipError_t he = e->bed.ensure((size_t)padded_rows(n_snp) * (size_t)row_pitch(n_org));
     if (he == hipSuccess) he = e->lastb.ensure((size_t)n_snp);
@@ -452,6 +458,28 @@ hipError_t load_slice(nldsc_engine* e, const uint8_t* src, int32_t row0, int32_t
                                     e->lastb.p, keep_compat, keep_strict, e->miss_flags.p, e->lcounts.p, st);
 }
 
+// Loads with a keep list: the file's individual count must be the list's; *n_img = the image's individuals (the kept
+// count, or n_org without a list)
+int keep_dims(const nldsc_engine* e, int32_t n_org, int32_t* n_img, char* err, size_t errlen) {
+    *n_img = n_org;
+    if (e->keep_n == 0) return NLDSC_OK;
+    if (n_org != e->keep_n_file)
+        return set_err(err, errlen, NLDSC_E_ARG, "n_org %d is not the keep list's file count %d", n_org, e->keep_n_file);
+    *n_img = e->keep_n;
+    return NLDSC_OK;
+}
+
+// load_slice of the kept samples of a slice of the file's rows (pitch nb_file): compacted into `compact` (n_rows rows
+// of ceil(keep_n / 4) bytes, launch_subset_slice), then placed as a slice of keep_n individuals, on one stream
+hipError_t load_slice_keep(nldsc_engine* e, const uint8_t* src, size_t nb_file, uint8_t* compact, int32_t row0,
+                           int32_t n_rows, int32_t n_snp, hipStream_t st) {
+    hipError_t he = nldsc::launch_subset_slice(src, (int)nb_file, n_rows, e->keep_idx.p, e->keep_n, compact, st);
+    if (he == hipSuccess) he = load_slice(e, compact, row0, n_rows, n_snp, e->keep_n, st);
+    return he;
+}
+
+size_t round16(size_t n) { return (n + 15) / 16 * 16; }
+
 // after every slice is in: per-row missing flags, the missing-free block counts, and mark the image valid
 hipError_t finish_image(nldsc_engine* e, int32_t n_snp, int32_t n_org) {
     hipError_t he = nldsc::launch_load_flags(e->miss_flags.p, n_snp, e->row_miss.p, e->stream);
@@ -469,6 +497,7 @@ hipError_t finish_image(nldsc_engine* e, int32_t n_snp, int32_t n_org) {
     if (he == hipSuccess) {
         e->n_snp = n_snp;
         e->n_org = n_org;
+        e->kept = e->keep_n;  // (loads with a list pass n_org = keep_n)
     }
     return he;
 }
@@ -592,6 +621,34 @@ void nldsc_host_free(void* p) {
     (void)hipHostFree(p);
 }
 
+int nldsc_engine_set_keep(nldsc_engine* e, const int32_t* idx, int32_t n_keep, int32_t n_org_file, char* err,
+                          size_t errlen) {
+    if (!e) return set_err(err, errlen, NLDSC_E_ARG, "NULL engine");
+    if (!idx) {  // no list: the next loads take every individual
+        e->keep_n = e->keep_n_file = 0;
+        return NLDSC_OK;
+    }
+    if (n_keep < 1 || n_keep > n_org_file)
+        return set_err(err, errlen, NLDSC_E_ARG, "keep list: need 1 <= n_keep <= n_org_file (got %d of %d)", n_keep,
+                       n_org_file);
+    for (int32_t k = 0; k < n_keep; ++k)
+        if (idx[k] < 0 || idx[k] >= n_org_file || (k > 0 && idx[k] <= idx[k - 1]))
+            return set_err(err, errlen, NLDSC_E_ARG,
+                           "keep list: entry %d (%d) is outside [0, %d) or not above the entry before it", k, idx[k],
+                           n_org_file);
+    HIPCHK(hipSetDevice(e->device));
+    e->keep_n = e->keep_n_file = 0;  // (no list while the copy may fail)
+    HIPCHK(e->keep_idx.ensure((size_t)n_keep));
+    // (the engine stream orders the copy after an earlier load's kernels that read the old list)
+    HIPCHK(hipMemcpyAsync(e->keep_idx.p, idx, sizeof(int32_t) * (size_t)n_keep, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->keep_n = n_keep;
+    e->keep_n_file = n_org_file;
+    return NLDSC_OK;
+}
+
+int nldsc_engine_kept(const nldsc_engine* e) { return e ? e->kept : NLDSC_E_ARG; }
+
 int nldsc_engine_load_bed_host(nldsc_engine* e, const uint8_t* bed, size_t len, int32_t n_snp, int32_t n_org,
                                char* err, size_t errlen) {
     if (!e || !bed) return set_err(err, errlen, NLDSC_E_ARG, "NULL engine or buffer");
@@ -599,19 +656,28 @@ int nldsc_engine_load_bed_host(nldsc_engine* e, const uint8_t* bed, size_t len, 
     if (rc) return rc;
     rc = check_magic(bed, len, n_snp, n_org, err, errlen);
     if (rc) return rc;
+    int32_t n_img = 0;
+    rc = keep_dims(e, n_org, &n_img, err, errlen);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(e->device));
-    const size_t nb = (size_t)(n_org / 4 + (n_org % 4 > 0));
-    HIPCHK(alloc_image(e, n_snp, n_org));
+    const size_t nb = (size_t)(n_org / 4 + (n_org % 4 > 0)), nb_img = (size_t)(n_img / 4 + (n_img % 4 > 0));
+    HIPCHK(alloc_image(e, n_snp, n_img));
     // rows go up in slices of ~64 MiB of whole 32-SNP blocks into a device staging buffer, then into the resident
     // layout (load_slice); the stream orders each slice's kernels before the next copy over the same staging bytes
     const size_t rows_per = std::max<size_t>(32, (size_t(64) << 20) / nb / 32 * 32);
-    HIPCHK(e->stage_dev.ensure(std::min(rows_per, (size_t)n_snp) * nb + 16));
+    // (with a keep list: a second region takes the slice compacted to the kept samples, which load_slice then places)
+    const size_t rows_max = std::min(rows_per, (size_t)n_snp), src_bytes = round16(rows_max * nb + 16);
+    HIPCHK(e->stage_dev.ensure(e->keep_n ? src_bytes + rows_max * nb_img + 16 : rows_max * nb + 16));
     for (size_t r0 = 0; r0 < (size_t)n_snp; r0 += rows_per) {
         const size_t nr = std::min(rows_per, (size_t)n_snp - r0);
         HIPCHK(hipMemcpyAsync(e->stage_dev.p, bed + 3 + r0 * nb, nr * nb, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(load_slice(e, e->stage_dev.p, (int)r0, (int)nr, n_snp, n_org, e->stream));
+        if (e->keep_n)
+            HIPCHK(load_slice_keep(e, e->stage_dev.p, nb, e->stage_dev.p + src_bytes, (int)r0, (int)nr, n_snp,
+                                   e->stream));
+        else
+            HIPCHK(load_slice(e, e->stage_dev.p, (int)r0, (int)nr, n_snp, n_org, e->stream));
     }
-    HIPCHK(finish_image(e, n_snp, n_org));
+    HIPCHK(finish_image(e, n_snp, n_img));
     e->stage_dev.release();
     return NLDSC_OK;
 }
@@ -620,6 +686,9 @@ int nldsc_engine_load_bed_device(nldsc_engine* e, const void* bed, size_t len, i
                                  char* err, size_t errlen) {
     if (!e || !bed) return set_err(err, errlen, NLDSC_E_ARG, "NULL engine or buffer");
     int rc = check_dims(n_snp, n_org, err, errlen);
+    if (rc) return rc;
+    int32_t n_img = 0;
+    rc = keep_dims(e, n_org, &n_img, err, errlen);
     if (rc) return rc;
     const size_t need = bed_bytes_needed(n_snp, n_org);
     if (len < 3) return set_err(err, errlen, NLDSC_E_BAD_MAGIC, "%s", kBadMagic);
@@ -630,7 +699,22 @@ int nldsc_engine_load_bed_device(nldsc_engine* e, const void* bed, size_t len, i
         return set_err(err, errlen, NLDSC_E_BAD_MAGIC, "%s", kBadMagic);
     if (len < need)
         return set_err(err, errlen, NLDSC_E_SIZE, "BED image too short: %zu bytes, expected at least %zu", len, need);
-    HIPCHK(alloc_image(e, n_snp, n_org));
+    HIPCHK(alloc_image(e, n_snp, n_img));
+    if (e->keep_n) {
+        // the kept samples go through a staging region in row slices of whole 32-SNP blocks, ~64 MiB of compact rows
+        // each (the stream orders a slice's placement before the next slice's compaction over the same bytes)
+        const size_t nb = (size_t)(n_org / 4 + (n_org % 4 > 0)), nb_img = (size_t)(n_img / 4 + (n_img % 4 > 0));
+        const size_t rows_per = std::max<size_t>(32, (size_t(64) << 20) / nb_img / 32 * 32);
+        HIPCHK(e->stage_dev.ensure(std::min(rows_per, (size_t)n_snp) * nb_img + 16));
+        for (size_t r0 = 0; r0 < (size_t)n_snp; r0 += rows_per) {
+            const size_t nr = std::min(rows_per, (size_t)n_snp - r0);
+            HIPCHK(load_slice_keep(e, static_cast<const uint8_t*>(bed) + 3 + r0 * nb, nb, e->stage_dev.p, (int)r0,
+                                   (int)nr, n_snp, e->stream));
+        }
+        HIPCHK(finish_image(e, n_snp, n_img));
+        e->stage_dev.release();
+        return NLDSC_OK;
+    }
     HIPCHK(load_slice(e, static_cast<const uint8_t*>(bed) + 3, 0, n_snp, n_snp, n_org, e->stream));
     HIPCHK(finish_image(e, n_snp, n_org));
     return NLDSC_OK;
@@ -644,6 +728,9 @@ int nldsc_engine_load_bed_file_range(nldsc_engine* e, const char* path, int32_t 
     if (snp_begin < 0 || snp_end > n_snp_file || snp_begin >= snp_end)
         return set_err(err, errlen, NLDSC_E_ARG, "SNP range [%d, %d) outside [0, %d) or empty", snp_begin, snp_end,
                        n_snp_file);
+    int32_t n_img = 0;
+    rc = keep_dims(e, n_org, &n_img, err, errlen);
+    if (rc) return rc;
     FILE* f = std::fopen(path, "rb");
     if (!f) {
         // the reference's ifstream fails silently and then rejects the (unread) magic number
@@ -670,7 +757,7 @@ int nldsc_engine_load_bed_file_range(nldsc_engine* e, const char* path, int32_t 
     HIPCHK(hipSetDevice(e->device));
     const int32_t n_snp = snp_end - snp_begin;
     {
-        const hipError_t ha = alloc_image(e, n_snp, n_org);
+        const hipError_t ha = alloc_image(e, n_snp, n_img);
         if (ha != hipSuccess) {
             std::fclose(f);
             return set_err(err, errlen, NLDSC_E_HIP, "HIP error %s allocating the image", hipGetErrorString(ha));
@@ -691,7 +778,11 @@ int nldsc_engine_load_bed_file_range(nldsc_engine* e, const char* path, int32_t 
         std::fclose(f);
         return set_err(err, errlen, NLDSC_E_OOM, "cannot allocate pinned staging buffer");
     }
-    hipError_t he = e->stage_dev.ensure((size_t)T * CH + 16);
+    // (with a keep list: T more slots after the file's, each a slice compacted to the kept samples)
+    const size_t nb_img = (size_t)(n_img / 4 + (n_img % 4 > 0));
+    const size_t src_bytes = round16((size_t)T * CH + 16), CH_img = round16(rows_per * nb_img);
+    const bool keep = e->keep_n != 0;
+    hipError_t he = e->stage_dev.ensure(keep ? src_bytes + (size_t)T * CH_img + 16 : (size_t)T * CH + 16);
     std::vector<hipStream_t> streams(T, nullptr);
     std::vector<hipEvent_t> done(T, nullptr);
     for (int t = 0; t < T && he == hipSuccess; ++t) {
@@ -728,7 +819,9 @@ int nldsc_engine_load_bed_file_range(nldsc_engine* e, const char* path, int32_t 
             }
             r = hipMemcpyAsync(dslot, buf, n, hipMemcpyHostToDevice, streams[t]);
             if (r == hipSuccess)
-                r = load_slice(e, dslot, (int)(off / nb), (int)(n / nb), n_snp, n_org, streams[t]);
+                r = keep ? load_slice_keep(e, dslot, nb, dstage + src_bytes + (size_t)t * CH_img, (int)(off / nb),
+                                           (int)(n / nb), n_snp, streams[t])
+                         : load_slice(e, dslot, (int)(off / nb), (int)(n / nb), n_snp, n_org, streams[t]);
             if (r == hipSuccess) r = hipEventRecord(done[t], streams[t]);
             pending = true;
         }
@@ -753,7 +846,7 @@ int nldsc_engine_load_bed_file_range(nldsc_engine* e, const char* path, int32_t 
     if (short_at.load() != SIZE_MAX) return too_short(short_at.load());
     std::fclose(f);
     if (he != hipSuccess) return set_err(err, errlen, NLDSC_E_HIP, "HIP error %s loading BED", hipGetErrorString(he));
-    HIPCHK(finish_image(e, n_snp, n_org));
+    HIPCHK(finish_image(e, n_snp, n_img));
     return NLDSC_OK;
 }
 
@@ -790,7 +883,8 @@ struct RunShape {
 
 RunShape run_shape(const nldsc_engine* e, const nldsc_ld_params* p, int own_begin, int own_end, bool split) {
     const int M = p->n_snp, N = p->n_org, row_bytes = row_pitch(N), nblk = (M + BLK - 1) / BLK;
-    const bool strict = (p->flags & NLDSC_FLAG_STRICT_PLINK_ORDER) != 0;
+    // (an image of kept samples is laid out in PLINK's order, whatever the flag says: nldsc_engine_set_keep)
+    const bool strict = (p->flags & NLDSC_FLAG_STRICT_PLINK_ORDER) != 0 || e->kept > 0;
     // last .bed byte: bit pairs that are individuals for the reference (high pairs first,
     // stream.h:55-66) or for PLINK (low pairs first) — the rest are recoded as missing (-> 0)
     const int rem = N % 4;
@@ -1524,6 +1618,23 @@ int nldsc_ld_calculate(const nldsc_ld_params* p, nldsc_ld_result* r, char* err, 
     if (rc) return rc;
     rc = nldsc_engine_load_bed_file(e, p->bedfile, p->n_snp, p->n_org, err, errlen);
     if (!rc) rc = nldsc_engine_run(e, p, 0, p->n_snp, r, err, errlen);
+    nldsc_engine_destroy(e);
+    return rc;
+}
+
+int nldsc_ld_calculate_keep(const nldsc_ld_params* p, const int32_t* idx, int32_t n_keep, nldsc_ld_result* r,
+                            char* err, size_t errlen) {
+    if (!p || !r || !p->bedfile) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
+    nldsc_engine* e = nullptr;
+    int rc = nldsc_engine_create(p->device, &e, err, errlen);
+    if (rc) return rc;
+    rc = nldsc_engine_set_keep(e, idx, n_keep, p->n_org, err, errlen);
+    if (!rc) rc = nldsc_engine_load_bed_file(e, p->bedfile, p->n_snp, p->n_org, err, errlen);
+    if (!rc) {
+        nldsc_ld_params q = *p;
+        q.n_org = e->n_org;  // the kept count (p->n_org without a list)
+        rc = nldsc_engine_run(e, &q, 0, p->n_snp, r, err, errlen);
+    }
     nldsc_engine_destroy(e);
     return rc;
 }

@@ -38,6 +38,14 @@ hipError_t launch_load_slice(const uint8_t* src, int nb, int row0, int n_rows, i
                              bool orient, uint8_t* flip, uint8_t* last, uint32_t keep_compat, uint32_t keep_strict,
                              uint32_t* miss_flags, int* lcounts, hipStream_t st);
 hipError_t launch_load_flags(const uint32_t* miss_flags, int n_snp, uint8_t* row_miss, hipStream_t st);
+// Loads on a subset of the individuals: n_rows rows of a .bed slice (row r of nb_src bytes at src + r * nb_src, any
+// alignment) compacted to the samples idx[0 .. n_keep) (device memory, strictly ascending, each < 4 nb_src; PLINK's
+// order: sample s is bit pair s % 4, low pairs first, of byte s / 4) — kept sample k to pair k % 4 of byte k / 4 of
+// the row at dst + r * ceil(n_keep / 4), the last byte's unused pairs 00: the slice `plink --keep` would write, ready
+// for launch_load_slice with nb = ceil(n_keep / 4).  Every byte of the n_rows compact rows is written; nothing is
+// read outside the source rows.
+hipError_t launch_subset_slice(const uint8_t* src, int nb_src, int n_rows, const int* idx, int n_keep, uint8_t* dst,
+                               hipStream_t st);
 // per run: set each row's non-individual slots (last byte outside tail_keep, pitch padding) to `pad` (0x55 missing,
 // or 0x00 for the fp4 kernel) and its genotype counts — the load's lcounts (P parts; the loaders keep 1) plus the last byte's individual
 // pairs — to counts3[3 j + k] (one thread per row; no pass over the rows)

@@ -306,6 +306,116 @@ __global__ void load_flags_kernel(const uint32_t* __restrict__ miss_flags, int n
     if (j < n_snp) row_miss[j] = (uint8_t)miss_flags[j];
 }
 
+// ---- loads on a subset of the individuals: a .bed slice compacted to the kept samples (what `plink --keep` writes) ----
+// Sample s of a .bed row is bit pair s % 4 (low pairs first) of byte s / 4 (PLINK's order).  idx[n_keep], strictly
+// ascending, names the kept samples; kept sample k goes to pair k % 4 of byte k / 4 of the compact row (nb_dst =
+// ceil(n_keep / 4) bytes; the last byte's unused pairs 00).  The compact slice then goes through the loads above as an
+// ordinary slice of n_keep individuals.
+// A workgroup takes 32 rows x SUB_WORDS output words of 16 codes: lane l of every wave holds word w0 + l (its 16 idx
+// loads, byte offsets and pair shifts), wave w builds that word for rows 8 w .. 8 w + 7, so all four waves gather from
+// every piece (one word per thread over all 32 rows left three waves in four waiting at the barrier while one
+// gathered: 6.4 ms per C3 image against 2.4 ms for the load itself).  idx is sorted, so those words' source bytes are
+// one span per row; it goes through LDS in pieces of SUB_PIECE bytes per row (32 threads per row segment, one 16-byte
+// load each, no further than the span's last byte), every piece starting at the byte of the first sample not yet
+// gathered (a sparse list skips the bytes between its samples' pieces; the next start is the smallest byte past the
+// piece among the lanes' codes, one ballot per wave, the same in every wave).  Per piece a thread extracts those of
+// its codes whose byte lies inside: one LDS byte read, one bit-field extract and one shift-or per code and row.
+// Source reads stay inside their rows (16-byte loads only for units wholly inside, single bytes for a row's last
+// unit), every byte of every output row is written exactly once, by one thread (whole words as one unaligned 4-byte
+// store, a row's last 1-3 bytes singly).
+constexpr int SUB_WORDS = 64;    // output words per workgroup (one per lane): 256 bytes of each compact row
+constexpr int SUB_PIECE = 512;   // source bytes per row and piece (LDS: 32 rows x (SUB_PIECE + 16) bytes)
+struct __attribute__((packed, aligned(1))) Word1 {
+    uint32_t v;
+};
+__global__ void __launch_bounds__(256) subset_samples_kernel(const uint8_t* __restrict__ src, int nb_src, int n_rows,
+                                                             const int* __restrict__ idx, int n_keep,
+                                                             uint8_t* __restrict__ dst, int nb_dst, int n_wr) {
+    constexpr int PITCH = SUB_PIECE + 16;  // (rows 528 bytes apart in LDS, as the tiled load's)
+    __shared__ __attribute__((aligned(16))) uint8_t piece[32 * PITCH];
+    const int rb = blockIdx.x / n_wr, wr = blockIdx.x % n_wr;
+    const int row_lo = 32 * rb, rows_here = min(32, n_rows - row_lo);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int wi = wr * SUB_WORDS + lane;  // this thread's output word (16 codes), for rows 8 w .. 8 w + 7
+    // kept samples [first, last] of the workgroup's words
+    const int first = wr * SUB_WORDS * 16, last = (int)min((long long)n_keep, (long long)first + SUB_WORDS * 16) - 1;
+    if (first > last) return;  // (never: the grid covers words of kept samples only)
+    // the thread's codes: source byte of the row and the pair's bit offset (codes past n_keep: no source, stay 00)
+    int off[16];
+    uint32_t sh[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const long long s = 16LL * wi + k;
+        const int v = s < n_keep ? idx[s] : -1;
+        off[k] = v >= 0 ? v >> 2 : INT_MAX;
+        sh[k] = 2u * (uint32_t)(v & 3);
+    }
+    uint32_t acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0u;
+    // the stage reader: thread tid takes unit tid % 32 of the piece in rows tid / 32 + 8 q
+    const int uu = threadIdx.x & 31, rr0 = threadIdx.x >> 5;
+    const int span_hi = idx[last] >> 2;  // the last source byte the workgroup needs
+    int pb = idx[first] >> 2;            // the piece: bytes [pb, pb + SUB_PIECE) of every row
+    while (true) {
+        const int p0 = pb + 16 * uu;
+        if (p0 <= span_hi) {  // (span_hi < nb_src)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int rr = rr0 + 8 * q;
+                if (rr < rows_here) {
+                    const size_t gbase = (size_t)(row_lo + rr) * (size_t)nb_src;
+                    const uint4 v = p0 + 16 <= nb_src ? load16_unaligned(src, gbase + (size_t)p0)
+                                                      : load16_bytes(src + gbase, p0, nb_src, 0u);
+                    *reinterpret_cast<uint4*>(piece + rr * PITCH + 16 * uu) = v;
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t rel = (uint32_t)(off[k] - pb);  // (off >= pb for every code not yet gathered)
+            if (off[k] >= pb && rel < (uint32_t)SUB_PIECE) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const uint32_t byte = piece[(8 * w + j) * PITCH + rel];
+                    acc[j] |= ((byte >> sh[k]) & 3u) << (2 * k);
+                }
+            }
+        }
+        // the next piece starts at the byte of the first code past this one: codes are sorted along k and the lanes,
+        // so it is the smallest such byte of the first lane holding one (INT_MAX: no code left; the codes past
+        // n_keep are INT_MAX already) — every wave holds the same codes and finds the same byte
+        int nxt = INT_MAX;
+#pragma unroll
+        for (int k = 15; k >= 0; --k)
+            if (off[k] - pb >= SUB_PIECE) nxt = off[k];
+        const unsigned long long have = __ballot(nxt != INT_MAX);
+        const int pb_next = __shfl(nxt, have ? __ffsll((long long)have) - 1 : 0, 64);
+        if (pb_next == INT_MAX) break;
+        __syncthreads();  // (the piece is rewritten after it)
+        pb = pb_next;
+    }
+    // bytes [4 wi, 4 wi + 4) of the compact rows, as far as they lie inside the row
+    const long long b0 = 4LL * wi;
+    if (b0 >= nb_dst) return;
+    const int nbytes = (int)min(4LL, (long long)nb_dst - b0);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int r = 8 * w + j;
+        if (r < rows_here) {
+            uint8_t* o = dst + (size_t)(row_lo + r) * (size_t)nb_dst + (size_t)b0;
+            if (nbytes == 4) {
+                reinterpret_cast<Word1*>(o)->v = acc[j];
+            } else {
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    if (q < nbytes) o[q] = (uint8_t)(acc[j] >> (8 * q));
+            }
+        }
+    }
+}
+
 
 // Halo pairs computed once across ranks (nldsc_engine_run_device_split): only pairs whose lower SNP lies in
 // [pair_lo, pair_hi) — the rank's owned range — keep flag bit 3 (snp_stats_kernel sets it on every SNP); the pairs of
@@ -2952,6 +3062,19 @@ hipError_t launch_load_slice(const uint8_t* src, int nb, int row0, int n_rows, i
     const int nblk = (n_rows + 31) / 32, P = load_parts(n_snp, row_bytes);
     hipLaunchKernelGGL(load_tiled_kernel, dim3(nblk * P), dim3(256), 0, st, src, nb, row0, n_rows, n_snp, img,
                        row_bytes, P, flip, last, keep_compat, keep_strict, miss_flags, lcounts);
+    return hipGetLastError();
+}
+
+hipError_t launch_subset_slice(const uint8_t* src, int nb_src, int n_rows, const int* idx, int n_keep, uint8_t* dst,
+                               hipStream_t st) {
+    if (n_rows <= 0) return hipSuccess;
+    if (n_keep <= 0 || (n_keep + 3) / 4 > nb_src) return hipErrorInvalidValue;
+    const int nb_dst = n_keep / 4 + (n_keep % 4 > 0), n_words = (nb_dst + 3) / 4;
+    const int n_wr = (n_words + SUB_WORDS - 1) / SUB_WORDS;
+    const long long blocks = (long long)((n_rows + 31) / 32) * n_wr;
+    if (blocks > INT_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(subset_samples_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, nb_src, n_rows, idx, n_keep,
+                       dst, nb_dst, n_wr);
     return hipGetLastError();
 }
 

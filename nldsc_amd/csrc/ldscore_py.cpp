@@ -7,8 +7,10 @@
 // `calculate` raises RuntimeError.
 //
 // Differences from the reference, all additive: the GIL is released during `calculate`;
-// LDScoreParams has two extra attributes, `flags` (NLDSC_FLAG_*) and `device` (HIP ordinal,
-// default from $NLDSC_DEVICE, else the current device); errors carry the engine's message.
+// LDScoreParams has three extra attributes, `flags` (NLDSC_FLAG_*), `device` (HIP ordinal,
+// default from $NLDSC_DEVICE, else the current device) and `keep` (0-based .fam line numbers of the
+// individuals to use, strictly ascending; empty: everyone — nldsc_ld_calculate_keep); errors carry
+// the engine's message.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -34,6 +36,7 @@ struct LDScoreParams {  // data.h:33-65
     double rsq_thr = 0;
     unsigned flags = 0;
     int device = -1;
+    std::vector<int> keep;  // .fam lines of the individuals to use (empty: everyone); n_org stays the file's count
 
     LDScoreParams() {
         if (const char* d = std::getenv("NLDSC_DEVICE")) device = std::atoi(d);
@@ -87,7 +90,9 @@ LDScoreResult calculate(const LDScoreParams& params) {
     int rc;
     {
         py::gil_scoped_release nogil;
-        rc = nldsc_ld_calculate(&p, &r, err, sizeof(err));
+        rc = params.keep.empty() ? nldsc_ld_calculate(&p, &r, err, sizeof(err))
+                                 : nldsc_ld_calculate_keep(&p, reinterpret_cast<const int32_t*>(params.keep.data()),
+                                                           (int32_t)params.keep.size(), &r, err, sizeof(err));
     }
     if (rc == NLDSC_E_BAD_MAGIC) throw std::invalid_argument(err);  // -> ValueError, as the reference
     if (rc != NLDSC_OK) throw std::runtime_error(err);
@@ -112,7 +117,8 @@ PYBIND11_MODULE(_ldscore, m) {
         .def_readwrite("std_thr", &LDScoreParams::std_thr)
         .def_readwrite("rsq_thr", &LDScoreParams::rsq_thr)
         .def_readwrite("flags", &LDScoreParams::flags)
-        .def_readwrite("device", &LDScoreParams::device);
+        .def_readwrite("device", &LDScoreParams::device)
+        .def_readwrite("keep", &LDScoreParams::keep);
 
     py::class_<LDScoreResult> R(m, "LDScoreResult");
     R.def(py::init());

@@ -199,10 +199,12 @@ def calculate_sharded(load_and_run: Callable[[tuple[int, int]], dict], positions
 
 
 def calculate_sharded_device(bed_path: str, n_snp: int, n_org: int, ld_wind: float, maf: float, std_thr: float,
-                             rsq_thr: float, positions: np.ndarray, *, flags: int = 0, device: int = 0) -> dict | None:
+                             rsq_thr: float, positions: np.ndarray, *, flags: int = 0, device: int = 0,
+                             keep=None) -> dict | None:
     """The RCCL path of `calculate_sharded` + `engine_runner`: this rank's engine reads its halo_range of the .bed,
     writes its owned slice of the score table straight into a device block (nldsc_engine_run_device), and the
-    blocks are gathered device to device; only rank 0's gathered table crosses to the host."""
+    blocks are gathered device to device; only rank 0's gathered table crosses to the host.  `keep`: the individuals
+    to use (Engine.set_keep; n_org stays the file's count)."""
     import torch
     import torch.distributed as dist
     from .engine import Engine
@@ -216,6 +218,7 @@ def calculate_sharded_device(bed_path: str, n_snp: int, n_org: int, ld_wind: flo
     if hi > lo:
         a, b = halo_range(pos, ld_wind, own)
         with Engine(device) as e:
+            e.set_keep(keep, n_org)
             e.load_bed_file_range(bed_path, n_snp, n_org, a, b)
             e.run_device(ld_wind, maf, std_thr, rsq_thr, pos[a:b], tab, own=(lo - a, hi - a), flags=flags)
     return gather_table(tab, spans, n_snp)
@@ -272,10 +275,10 @@ def exchange_halo(export, n_send: int, imported, n_recv: int):
 
 def calculate_sharded_split(bed_path: str, n_snp: int, n_org: int, ld_wind: float, maf: float, std_thr: float,
                             rsq_thr: float, positions: np.ndarray, plan: list[tuple[int, int, int]], *, flags: int = 0,
-                            device: int = 0) -> dict | None:
+                            device: int = 0, keep=None) -> dict | None:
     """The sharded CLI run with each boundary pair computed once (`split_plan`): this rank loads [lo, b) of the .bed,
     runs the first half of a split run, sends its right halo's sums to the next rank, adds the previous rank's, and
-    finishes; the score-table blocks are then gathered as in calculate_sharded_device."""
+    finishes; the score-table blocks are then gathered as in calculate_sharded_device (`keep` as there)."""
     import torch
     import torch.distributed as dist
     from .engine import Engine
@@ -290,6 +293,7 @@ def calculate_sharded_split(bed_path: str, n_snp: int, n_org: int, ld_wind: floa
     export = torch.empty(6 * max(b - hi, 1), dtype=torch.int64, device=dev)
     imported = torch.empty(6 * max(n_recv, 1), dtype=torch.int64, device=dev)
     with Engine(device) as e:
+        e.set_keep(keep, n_org)
         e.load_bed_file_range(bed_path, n_snp, n_org, lo, b)
         n_send = e.run_device_split(ld_wind, maf, std_thr, rsq_thr, pos[lo:b], tab, export, own=(0, hi - lo),
                                     flags=flags)
@@ -299,10 +303,11 @@ def calculate_sharded_split(bed_path: str, n_snp: int, n_org: int, ld_wind: floa
 
 
 def engine_runner(bed_path: str, n_snp: int, n_org: int, ld_wind: float, maf: float, std_thr: float,
-                  rsq_thr: float, positions: np.ndarray, *, flags: int = 0, device: int = 0):
+                  rsq_thr: float, positions: np.ndarray, *, flags: int = 0, device: int = 0, keep=None):
     """`load_and_run` for calculate_sharded backed by this rank's GPU engine: the rank reads only its
     `halo_range` of the .bed (one window around its owned SNPs) and computes the owned SNPs on that
-    slice; rsq_thr stays the whole chromosome's (1/M)."""
+    slice; rsq_thr stays the whole chromosome's (1/M).  `keep`: the individuals to use (Engine.set_keep; n_org stays
+    the file's count)."""
     pos = np.asarray(positions, dtype=np.float64)
 
     def run(own):
@@ -313,6 +318,7 @@ def engine_runner(bed_path: str, n_snp: int, n_org: int, ld_wind: float, maf: fl
             return res
         a, b = halo_range(pos, ld_wind, own)
         with Engine(device) as e:
+            e.set_keep(keep, n_org)
             e.load_bed_file_range(bed_path, n_snp, n_org, a, b)
             part = e.run(ld_wind, maf, std_thr, rsq_thr, pos[a:b], own=(lo - a, hi - a), flags=flags)
         for k in RESULT_KEYS:

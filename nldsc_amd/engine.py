@@ -66,17 +66,41 @@ class Engine:
         self.close()
 
     # ---- loading ------------------------------------------------------------------------
+    def set_keep(self, indices, n_org_file: int = 0):
+        """Keep only these individuals in the next loads (C ABI nldsc_engine_set_keep): `indices` are 0-based .fam
+        line numbers, strictly ascending, of a file of n_org_file individuals; None (or empty) clears the list.  With
+        a list the loaders take n_org = n_org_file and leave `self.n_org` at the kept count; runs on such an image
+        use PLINK's sample order whatever their flags."""
+        err = _lib.errbuf()
+        if indices is None or len(indices) == 0:
+            _lib.check(self._L.nldsc_engine_set_keep(self._h, None, 0, 0, err, len(err)), err)
+            return
+        idx = np.asarray(indices)
+        if idx.ndim != 1 or idx.dtype.kind not in "iu" or (idx.size and (idx.min() < -2**31 or idx.max() >= 2**31)):
+            raise ValueError("keep indices must be a 1-D sequence of 32-bit integers")
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        _lib.check(self._L.nldsc_engine_set_keep(self._h, idx.ctypes.data, len(idx), int(n_org_file), err, len(err)),
+                   err)
+
+    def kept(self) -> int:
+        """Kept individuals of the resident image when it was loaded with a keep list, else 0."""
+        return int(self._L.nldsc_engine_kept(self._h))
+
+    def _loaded(self, n_snp: int, n_org: int):
+        k = self.kept() if hasattr(self._L, "nldsc_engine_kept") else 0
+        self.n_snp, self.n_org = n_snp, (k if k > 0 else n_org)
+
     def load_bed_file(self, path: str, n_snp: int, n_org: int):
         err = _lib.errbuf()
         _lib.check(self._L.nldsc_engine_load_bed_file(self._h, path.encode(), n_snp, n_org, err, len(err)), err)
-        self.n_snp, self.n_org = n_snp, n_org
+        self._loaded(n_snp, n_org)
 
     def load_bed_file_range(self, path: str, n_snp_file: int, n_org: int, begin: int, end: int):
         """Rows [begin, end) of a .bed file of n_snp_file SNPs (position sharding: own range + halo)."""
         err = _lib.errbuf()
         _lib.check(self._L.nldsc_engine_load_bed_file_range(self._h, path.encode(), n_snp_file, n_org, int(begin),
                                                                int(end), err, len(err)), err)
-        self.n_snp, self.n_org = int(end) - int(begin), n_org
+        self._loaded(int(end) - int(begin), n_org)
 
     def load_bed_bytes(self, bed, n_snp: int, n_org: int):
         """`bed`: the whole .bed content (bytes / uint8 numpy array), magic included."""
@@ -84,14 +108,14 @@ class Engine:
         err = _lib.errbuf()
         _lib.check(self._L.nldsc_engine_load_bed_host(self._h, buf.ctypes.data, buf.nbytes, n_snp, n_org, err,
                                                          len(err)), err)
-        self.n_snp, self.n_org = n_snp, n_org
+        self._loaded(n_snp, n_org)
 
     def load_bed_device(self, ptr: int, nbytes: int, n_snp: int, n_org: int):
         """Copy a .bed image that already lives in this device's memory (e.g. a torch tensor)."""
         err = _lib.errbuf()
         _lib.check(self._L.nldsc_engine_load_bed_device(self._h, ctypes.c_void_p(ptr), nbytes, n_snp, n_org, err,
                                                            len(err)), err)
-        self.n_snp, self.n_org = n_snp, n_org
+        self._loaded(n_snp, n_org)
 
     # ---- compute ------------------------------------------------------------------------
     def run(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, out=None):
@@ -184,13 +208,20 @@ class Engine:
         return d
 
 
-def calculate(bedfile: str, n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, *, flags=0, device=-1) -> dict:
-    """One-shot C-ABI call `nldsc_ld_calculate` (file -> GPU -> results)."""
-    p, _keep = _lib.make_params(n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, bedfile=bedfile,
-                                flags=flags, device=device)
+def calculate(bedfile: str, n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, *, flags=0, device=-1,
+              keep=None) -> dict:
+    """One-shot C-ABI call `nldsc_ld_calculate` (file -> GPU -> results); with `keep` (0-based .fam line numbers,
+    strictly ascending; n_org stays the file's count) `nldsc_ld_calculate_keep`, on those individuals only."""
+    p, _pos = _lib.make_params(n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, bedfile=bedfile,
+                               flags=flags, device=device)
     arrs, res = _lib.alloc_result(n_snp)
     err = _lib.errbuf()
-    _lib.check(_lib.lib().nldsc_ld_calculate(ctypes.byref(p), ctypes.byref(res), err, len(err)), err)
+    if keep is None or len(keep) == 0:
+        _lib.check(_lib.lib().nldsc_ld_calculate(ctypes.byref(p), ctypes.byref(res), err, len(err)), err)
+    else:
+        idx = np.ascontiguousarray(keep, dtype=np.int32)
+        _lib.check(_lib.lib().nldsc_ld_calculate_keep(ctypes.byref(p), idx.ctypes.data, len(idx), ctypes.byref(res),
+                                                      err, len(err)), err)
     return arrs
 
 

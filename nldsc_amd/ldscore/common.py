@@ -4,6 +4,8 @@ The reference's public names, validation rules and messages, 
   LDWindow               kb -> bp x 1000; > 0; <= 5 Mbp or <= 100 cM
   PLINKFile.parse        prefix or one of the three paths -> (BEDFile, BIMFile, FAMFile)
   BIMFile / FAMFile      tab-separated tables, one chromosome per .bim; n_snp / n_org = number of lines
+  read_id_file, kept_individuals   --keep / --remove lists (FID IID per line) -> .fam line numbers (no reference
+                         counterpart: PLINK's / LDSC's flags of the same names)
   MAF, ResidualsSTDThreshold, RSQThreshold: [0, 1), [0, 1), [0, 0.1)
 (RSQThreshold's repr says `std_thr=`, as the reference's does.)
 """
@@ -12,12 +14,14 @@ from __future__ import annotations
 import os
 from pathlib import Path
 
+import numpy as np
 import pandas as pd
 
 from ..core.common import Data, NLDSCParameterError
+from ..core.logger import log
 
 __all__ = ["LDWindow", "PLINKFile", "BEDFile", "BIMFile", "FAMFile", "MAF", "ResidualsSTDThreshold",
-           "RSQThreshold", "NLDSCParameterError"]
+           "RSQThreshold", "NLDSCParameterError", "read_id_file", "kept_individuals"]
 
 # window metric -> (largest window, how the message names it)
 _WINDOW_LIMITS = {"bp": (5 * 10 ** 6, "5 Mbp"), "cm": (100, "100 cm")}
@@ -111,9 +115,9 @@ class BIMFile(PLINKFile):
 
 
 class FAMFile(PLINKFile):
-    """Only the number of individuals is used: it is counted from the lines (the rows pandas would parse: non-blank
-    lines; a whole-genome run reads 22 copies of a 315 599-line file, ~0.15 s each through pandas), and the table is
-    parsed when `data` is first asked for."""
+    """The number of individuals is counted from the lines (the rows pandas would parse: non-blank
+    lines; a whole-genome run reads 22 copies of a 315 599-line file, ~0.15 s each through pandas); the table is
+    parsed when `data` is first asked for, and the (FID, IID) pairs of the lines (--keep / --remove) when `ids` is."""
     EXT = ".fam"
     COLUMNS = ("FID", "IID", "FATHER", "MOTHER", "SEX", "TRAIT")
 
@@ -126,6 +130,24 @@ class FAMFile(PLINKFile):
             # only spaces (an empty file is 0 rows, as the reference's read_csv with `names` gives)
             self._n_org = sum(1 for line in fh.read().splitlines() if line.strip(b" "))
         self._table = None
+        self._ids = None
+
+    @property
+    def ids(self) -> list:
+        """(FID, IID) of every line, in file order: line s is individual s of every .bed row (PLINK: fields
+        separated by tabs or spaces)."""
+        if self._ids is None:
+            ids = []
+            with open(self._path, "rb") as fh:
+                for line in fh.read().splitlines():
+                    if not line.strip(b" "):
+                        continue
+                    f = line.split()
+                    if len(f) < 2:
+                        raise NLDSCParameterError(f'"{self._path}": a line with fewer than two fields (FID IID)')
+                    ids.append((f[0].decode(errors="replace"), f[1].decode(errors="replace")))
+            self._ids = ids
+        return self._ids
 
     @property
     def data(self) -> pd.DataFrame:
@@ -160,3 +182,46 @@ MAF = _threshold("MAF", "maf", 1.0, "Minor allele frequency must be between 0 an
 ResidualsSTDThreshold = _threshold("ResidualsSTDThreshold", "std_thr", 1.0,
                                    "standard deviation threshold must be between 0 and 1!")
 RSQThreshold = _threshold("RSQThreshold", "std_thr", 0.1, "r-squared threshold must be between 0 and 0.1!")
+
+
+def read_id_file(path: str) -> list:
+    """The (FID, IID) pairs of a --keep / --remove file: whitespace-separated `FID IID` per line, further columns
+    ignored, blank lines skipped; a line with fewer than two fields is an error."""
+    if not os.path.exists(str(path)):
+        raise FileNotFoundError(f'No such file: "{path}"')
+    ids = []
+    with open(str(path), "rb") as fh:
+        for n, line in enumerate(fh.read().splitlines(), 1):
+            f = line.split()
+            if not f:
+                continue
+            if len(f) < 2:
+                raise NLDSCParameterError(f'"{path}", line {n}: expected "FID IID", got fewer than two fields')
+            ids.append((f[0].decode(errors="replace"), f[1].decode(errors="replace")))
+    return ids
+
+
+def kept_individuals(fam: FAMFile, keep: str | None = None, remove: str | None = None):
+    """The individuals a run uses, as ascending 0-based .fam line numbers (int32 array), or None for everyone (no
+    file given): the .fam lines named in the `keep` file (everyone without one) minus those named in the `remove`
+    file.  The order is the .fam's; duplicates collapse (in the lists, and every .fam line with a listed ID counts);
+    IDs that are not in the .fam are counted in one warning per file.  An empty result is an error."""
+    if keep is None and remove is None:
+        return None
+    fam_ids = fam.ids
+    known = set(fam_ids)
+    lists = {}
+    for what, path in (("--keep", keep), ("--remove", remove)):
+        if path is None:
+            continue
+        ids = set(read_id_file(path))
+        unknown = len(ids - known)
+        if unknown:
+            log.warning(f"{what} {path}: {unknown} of {len(ids)} IDs are not in {fam._path}")
+        lists[what] = ids
+    keep_ids, remove_ids = lists.get("--keep"), lists.get("--remove", set())
+    idx = np.fromiter((s for s, i in enumerate(fam_ids)
+                       if (keep_ids is None or i in keep_ids) and i not in remove_ids), dtype=np.int32)
+    if idx.size == 0:
+        raise NLDSCParameterError("--keep / --remove leave no individual")
+    return idx

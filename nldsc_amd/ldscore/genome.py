@@ -18,7 +18,7 @@ import numpy as np
 
 from ..core.common import NLDSCParameterError, elapsed_time
 from ..core.logger import log
-from .common import FAMFile, BIMFile, LDWindow, MAF, ResidualsSTDThreshold, RSQThreshold
+from .common import FAMFile, BIMFile, LDWindow, MAF, ResidualsSTDThreshold, RSQThreshold, kept_individuals
 from .routine import m_values, make_output, write_m_file, write_scores
 
 CHROMS = [str(c) for c in range(1, 23)] + ["X", "Y", "XY", "MT"]
@@ -72,11 +72,14 @@ def _readahead(path: str) -> None:
         pass
 
 
-def _default_runner(device: int):
+def _default_runner(device: int, keep=None, n_org_file: int = 0):
     """The GPU engine, fed by its own file reader (file -> pinned slots -> pitched H2D copies overlapping
-    the reads, ~20 GB/s from the page cache) instead of a host array copied from pageable memory."""
+    the reads, ~20 GB/s from the page cache) instead of a host array copied from pageable memory.  `keep`: the
+    individuals every chromosome is computed on (set once: Engine.set_keep), of n_org_file in the files."""
     from ..engine import Engine
     eng = Engine(device)
+    if keep is not None:
+        eng.set_keep(keep, n_org_file)
 
     def run(bed_path: str, n_snp: int, n_org: int, ld_wind, maf, std_thr, rsq_thr, positions, flags):
         eng.load_bed_file(bed_path, n_snp, n_org)
@@ -90,9 +93,11 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
                         std_thr: float = 1e-5, rsq_thr: float | None = None, *, out: str | None = None,
                         extra: bool = False, write_m: bool = False, flags: int = 0, device: int | None = None,
                         runner=None, rank: int | None = None, world: int | None = None,
-                        progress: bool | None = None) -> dict:
+                        progress: bool | None = None, keep: str | None = None,
+                        remove: str | None = None) -> dict:
     """Returns {chromosome: output DataFrame (None when written to `out`)} for the chromosomes this rank
-    processed."""
+    processed.  `keep` / `remove`: `FID IID` lists as in estimate_lds; every chromosome's .fam must resolve to the
+    same individuals (a `runner` given by the caller then receives them as the keyword `keep`)."""
     units = expand_bfile(bfile)
     if out is not None and "@" not in out:
         raise NLDSCParameterError("a whole-genome run needs '@' in --out (one output per chromosome)")
@@ -103,8 +108,17 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
     # cheap host pass: .bim/.fam of every unit, pair-work estimate for the assignment
     from ..distributed import assign_units, window_work
     meta = []
+    kept, kept_n_file = None, 0
     for chrom, stem in units:
         bim, fam = BIMFile(stem + ".bim"), FAMFile(stem + ".fam")
+        if keep is not None or remove is not None:
+            k = kept_individuals(fam, keep, remove)
+            if kept is None:
+                kept, kept_n_file = k, fam.n_org
+                log.info(f"N = {len(kept)} of {fam.n_org}")
+            elif fam.n_org != kept_n_file or not np.array_equal(k, kept):
+                raise NLDSCParameterError(f"--keep / --remove select other individuals in {stem}.fam than in "
+                                          f"{units[0][1]}.fam: every chromosome needs the same .fam")
         pos = np.asarray(getattr(bim, ld_wind_.metric), dtype=np.float64)
         meta.append(dict(chrom=chrom, stem=stem, bim=bim, n_org=fam.n_org, pos=pos,
                          work=float(window_work(pos, ld_wind_.data).sum()) * fam.n_org))
@@ -117,7 +131,10 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
             local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _lib.lib().nldsc_device_count())
         else:
             local = int(device)
-        runner = _default_runner(local)
+        runner = _default_runner(local, kept, kept_n_file)
+        kept_kw = {}
+    else:
+        kept_kw = {} if kept is None else {"keep": kept}
     from ..core.progress import Progress
     total_snp = sum(meta[u]["bim"].n_snp for u in mine)
     bar = Progress(total_snp, "SNPs", label=f"ld rank {rank}" if world > 1 else "ld", enabled=progress,
@@ -143,7 +160,8 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
         n_snp = m["bim"].n_snp
         rsq = RSQThreshold(1.0 / n_snp if rsq_thr is None else rsq_thr).data
         t0 = time.perf_counter()
-        res, tim = runner(bed, n_snp, m["n_org"], ld_wind_.data, maf_thr_.data, std_thr_.data, rsq, m["pos"], flags)
+        res, tim = runner(bed, n_snp, m["n_org"], ld_wind_.data, maf_thr_.data, std_thr_.data, rsq, m["pos"], flags,
+                          **kept_kw)
         ld = _Res(res)
         df = make_output(m["bim"], ld, extra=extra) if out is None else None
         if out is not None:

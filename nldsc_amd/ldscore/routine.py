@@ -17,7 +17,7 @@ import pandas as pd
 from ..core.common import elapsed_time
 from ..core.logger import log
 from . import _ldscore as lds
-from .common import BIMFile, LDWindow, MAF, PLINKFile, ResidualsSTDThreshold, RSQThreshold
+from .common import BIMFile, LDWindow, MAF, PLINKFile, ResidualsSTDThreshold, RSQThreshold, kept_individuals
 
 __all__ = ["estimate_lds", "make_output", "format_scores", "write_scores", "show_summary", "m_values", "write_m_file"]
 
@@ -151,16 +151,19 @@ def _calculate_sharded(dist, params):
     from .. import distributed as D
     dev = _local_device()
     pos = np.asarray(params.positions, dtype=np.float64)
+    keep = np.asarray(params.keep, dtype=np.int32) if len(params.keep) else None
     plan = D.split_plan(pos, params.ld_wind, dist.get_world_size()) if _split_halo() else None
     if plan is not None:  # boundary pairs once: halo sums sent to the next rank (point to point)
         full = D.calculate_sharded_split(params.bedfile, params.n_snp, params.n_org, params.ld_wind, params.maf,
-                                         params.std_thr, params.rsq_thr, pos, plan, flags=params.flags, device=dev)
+                                         params.std_thr, params.rsq_thr, pos, plan, flags=params.flags, device=dev,
+                                         keep=keep)
     elif _backend() == "nccl":  # the owned slices stay in device memory and are gathered over RCCL
         full = D.calculate_sharded_device(params.bedfile, params.n_snp, params.n_org, params.ld_wind, params.maf,
-                                          params.std_thr, params.rsq_thr, pos, flags=params.flags, device=dev)
+                                          params.std_thr, params.rsq_thr, pos, flags=params.flags, device=dev,
+                                          keep=keep)
     else:  # gloo: host result arrays, CPU collectives
         run = D.engine_runner(params.bedfile, params.n_snp, params.n_org, params.ld_wind, params.maf,
-                              params.std_thr, params.rsq_thr, pos, flags=params.flags, device=dev)
+                              params.std_thr, params.rsq_thr, pos, flags=params.flags, device=dev, keep=keep)
         full = D.calculate_sharded(run, pos, params.ld_wind, params.n_snp)
     return None if full is None else _Result(full)
 
@@ -169,7 +172,9 @@ def _calculate_sharded(dist, params):
 def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 1e-5, std_thr: float = 1e-5,
                  rsq_thr: float | None = None, *, out: str | None = None, extra: bool = False, summary: bool = False,
                  verbose: int = 0, write_m: bool = False, flags: int = 0, device: int | None = None,
-                 progress: bool | None = None):
+                 progress: bool | None = None, keep: str | None = None, remove: str | None = None):
+    """`keep` / `remove`: paths of `FID IID` lists (PLINK's / LDSC's --keep, --remove): the scores are computed on the
+    .fam lines of the first minus those of the second, in PLINK's sample order (common.kept_individuals)."""
     bed_, bim_, fam_ = PLINKFile.parse(bfile)
     ld_wind_ = LDWindow(ld_wind, metric=wind_metric)
     maf_thr_ = MAF(maf_thr)
@@ -177,13 +182,19 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
     if rsq_thr is None:
         rsq_thr = 1.0 / bim_.n_snp
     rsq_thr_ = RSQThreshold(rsq_thr)
-    log.info(f"Input: {bed_.data}, size: (M={bim_.n_snp}, N={fam_.n_org})")
+    kept = kept_individuals(fam_, keep, remove)
+    if kept is None:
+        log.info(f"Input: {bed_.data}, size: (M={bim_.n_snp}, N={fam_.n_org})")
+    else:
+        log.info(f"Input: {bed_.data}, size: (M={bim_.n_snp}, N = {len(kept)} of {fam_.n_org})")
 
     params = lds.LDScoreParams(
         bfile=bed_.data, n_snp=bim_.n_snp, n_org=fam_.n_org, ld_wind=ld_wind_.data, maf=maf_thr_.data,
         std_thr=std_thr_.data, rsq_thr=rsq_thr_.data,
         positions=np.asarray(getattr(bim_, ld_wind_.metric), dtype=np.float64).tolist())
     params.flags = int(flags)
+    if kept is not None:
+        params.keep = kept.tolist()
     if device is not None:
         params.device = int(device)
     log.info("Running the estimator. It may take a long time.")
