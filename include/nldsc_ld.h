@@ -83,6 +83,12 @@ int nldsc_ld_calculate(const nldsc_ld_params* p, nldsc_ld_result* r, char* err, 
  * the file's individual count.  idx == NULL: everyone, as nldsc_ld_calculate. */
 int nldsc_ld_calculate_keep(const nldsc_ld_params* p, const int32_t* idx, int32_t n_keep, nldsc_ld_result* r,
                             char* err, size_t errlen);
+/* One-shot partitioned LD scores (nldsc_engine_run_annot below: the layout of `annot`, `l2_annot`, `l2d_annot` and the
+ * rules): read `p->bedfile`, on the individuals idx[n_keep] when idx != NULL (nldsc_ld_calculate_keep), fill `r` and
+ * the per-annotation scores of all n_snp SNPs. */
+int nldsc_ld_calculate_annot(const nldsc_ld_params* p, const int32_t* keep_idx, int32_t n_keep, const double* annot,
+                             int32_t n_annot, nldsc_ld_result* r, double* l2_annot, double* l2d_annot, char* err,
+                             size_t errlen);
 
 /* Library / device information. */
 const char* nldsc_version(void);
@@ -107,6 +113,7 @@ void nldsc_engine_destroy(nldsc_engine* e);
  *   f4_nc2       [1] additive-only fp4 items of two column blocks; 0 single block pairs
  *   q_rounds     [1] quad super-items in launches of one workgroup per CU; 0 one launch
  *   defer_rep    [1] K loops of items holding a replayed rare variant in the main launch; 0 a later KC launch
+ *   annot_batch_items [0] annotated runs: block-pair items per batch (0: what the Gram scratch cap holds)
  *   debug_timing [0] per-run stage timings on stderr */
 int nldsc_engine_set_option(nldsc_engine* e, const char* name, int64_t value, char* err, size_t errlen);
 
@@ -157,6 +164,28 @@ int nldsc_engine_kept(const nldsc_engine* e);
  * may be ordinary host memory or nldsc_host_alloc buffers (written by the GPU in place). */
 int nldsc_engine_run(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,
                      nldsc_ld_result* r, char* err, size_t errlen);
+
+/* Partitioned LD scores (stratified LD score regression; LDSC's --annot): nldsc_engine_run plus, for every
+ * annotation column c of `annot`, L2[j, c] = a[j, c] + sum_k a[k, c] r2adj(j, k) over SNP j's window (the a[j, c]
+ * is the self term, as the 1 of L2) and L2D[j, c] = sum_k a[k, c] r2adj_dominance(j, k) over the neighbours L2D
+ * counts.  `annot`, `l2_annot` and `l2d_annot` are category-major [n_annot][p->n_snp] host arrays; entries outside
+ * the owned range are left untouched.  `r` is filled exactly as nldsc_engine_run fills it, bit for bit.
+ *   - l2_annot[c][j] is NaN exactly where r->l2[j] is, l2d_annot[c][j] exactly where r->l2d[j] is.  l2d_annot may be
+ *     NULL with NLDSC_FLAG_ADDITIVE_ONLY; non-NULL with that flag it is filled with NaN.
+ *   - The sums accumulate as 64-bit integers in units of 2^(-44 + e_c), e_c = max(0, ceil(log2(max_j |a[j, c]|))): a
+ *     0/1 column has the resolution of L2 itself; what that rounding drops of each work item's partial sum goes to a
+ *     second integer accumulator in units of 2^-40 of the first, so a total carries the fp64 partial sums' precision.
+ *     Results do not depend on the schedule (engine options, batches, K-split) and are bit-reproducible.  Negative
+ *     values are allowed.
+ *   - NLDSC_E_ARG, with the reason in `err`, unless 1 <= n_annot <= NLDSC_MAX_ANNOT, every value of `annot` is
+ *     finite, the run takes the exact fp4 path (NLDSC_FLAG_FP32 / NLDSC_FLAG_EXACT_I8, or option band_mode 0 / 1,
+ *     are rejected) and n_org < 2^19.  Host results only: the device-table runs take no annotations.
+ *   - The band goes in batches of single block-pair items (option annot_batch_items, 0 = as many as 1 GiB of Gram
+ *     scratch holds), whatever the options t2, f4_nc2 and band_rounds say.  Stateless: the next run is a plain one. */
+#define NLDSC_MAX_ANNOT 1024
+int nldsc_engine_run_annot(nldsc_engine* e, const nldsc_ld_params* p, const double* annot, int32_t n_annot,
+                           int32_t own_begin, int32_t own_end, nldsc_ld_result* r, double* l2_annot,
+                           double* l2d_annot, char* err, size_t errlen);
 
 /* nldsc_engine_run with the owned slice of the result left in device memory (the multi-GPU gather of
  * SURVEY.md §8 e1 then runs device to device over RCCL, without a host round trip): `table_dev`, device memory
@@ -242,6 +271,15 @@ int nldsc_engine_load_bed_file_range(nldsc_engine* e, const char* path, int32_t 
  * arguments. */
 int nldsc_plan_band(const double* positions, const uint8_t* flags, int32_t n_snp, double ld_wind, int32_t own_begin,
                     int32_t own_end, int32_t max_nc, int32_t* L, int32_t* R, int32_t* items, int32_t cap);
+
+/* Host-only arithmetic of annotated runs (no GPU needed; the engine calls the same code).  _scale_exp: e_c of a
+ * column whose largest |a| is max_abs (0 for max_abs <= 1).  _plan_batches: the batches of a band of n_items items of
+ * n_it K-loop chunks on n_cu CUs, batches[3 k ..] = (first item, items, K-split pieces); batch_items as the engine
+ * option annot_batch_items.  Returns the batch count; when it exceeds `cap` (or batches == NULL) nothing is
+ * written; < 0 on bad arguments. */
+int nldsc_annot_scale_exp(double max_abs);
+int nldsc_annot_plan_batches(int32_t n_items, int32_t n_it, int32_t n_cu, int32_t ksplit_ok, int32_t batch_items,
+                             int32_t* batches, int32_t cap);
 
 /* The score table as the reference writes it (make_output + DataFrame.to_csv(sep="\t", index=False,
  * float_format="%.5f"), nldsc/ldscore/routine.py:94-101), without the header line: row i = prefix line i

@@ -55,13 +55,16 @@ def main():
                              "implies PLINK sample order (--strict-plink-order)", metavar="FILE", default=None)
 @click.option("--remove", help="Leave out the individuals listed in FILE (FID IID per line), as PLINK's --remove; "
                                "implies PLINK sample order (--strict-plink-order)", metavar="FILE", default=None)
+@click.option("--annot", help="Partitioned LD scores: FILE is an LDSC .annot / .annot.gz (with '@' for the chromosome "
+                              "in a whole-genome run); adds L2_<name> / L2D_<name> columns and, with --write-m, "
+                              "<out>.M_annot", metavar="FILE", default=None)
 @click.option("--additive-only", help="Skip the dominance terms (L2D = NaN)", is_flag=True, default=False)
 @click.option("--device", help="HIP device ordinal", type=int, default=None)
 @click.option("--quiet", help="No progress lines on stderr", is_flag=True, default=False)
 @click.option("--display", help="Display traceback", is_flag=True, default=False)
 @handle_exception
 def est_ld(bfile, out, ld_wind_kb, ld_wind_cm, maf_thr, std_thr, rsq_thr, extra, write_m, strict_plink_order,
-           keep, remove, additive_only, device, quiet):
+           keep, remove, annot, additive_only, device, quiet):
     if sum(map(bool, [ld_wind_kb, ld_wind_cm])) != 1:
         raise RuntimeError("Please, specify exactly one --ld-wind option")
     elif ld_wind_kb:
@@ -75,11 +78,11 @@ def est_ld(bfile, out, ld_wind_kb, ld_wind_cm, maf_thr, std_thr, rsq_thr, extra,
         from .ldscore.genome import estimate_lds_genome
         estimate_lds_genome(bfile, ld_wind=ld_wind, wind_metric=wind_metric, maf_thr=maf_thr, std_thr=std_thr,
                             rsq_thr=rsq_thr, out=out, extra=extra, write_m=write_m, flags=flags, device=device,
-                            progress=not quiet, keep=keep, remove=remove)
+                            progress=not quiet, keep=keep, remove=remove, annot=annot)
         return
     estimate_lds(bfile, ld_wind=ld_wind, wind_metric=wind_metric, maf_thr=maf_thr, std_thr=std_thr,
                  rsq_thr=rsq_thr, out=out, extra=extra, summary=True, write_m=write_m, flags=flags, device=device,
-                 progress=not quiet, keep=keep, remove=remove)
+                 progress=not quiet, keep=keep, remove=remove, annot=annot)
 
 
 @main.command("h2", help="(not part of this engine) heritability estimation")

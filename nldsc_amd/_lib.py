@@ -34,7 +34,9 @@ EXPORTED = (
     "nldsc_engine_band_tail_ksplit", "nldsc_engine_run_device", "nldsc_engine_run_device_split",
     "nldsc_engine_run_device_finish", "nldsc_engine_set_option", "nldsc_host_alloc", "nldsc_host_free",
     "nldsc_engine_result_direct", "nldsc_engine_set_keep", "nldsc_engine_kept", "nldsc_ld_calculate_keep",
+    "nldsc_engine_run_annot", "nldsc_ld_calculate_annot", "nldsc_annot_scale_exp", "nldsc_annot_plan_batches",
 )
+MAX_ANNOT = 1024  # NLDSC_MAX_ANNOT
 
 
 class Params(ctypes.Structure):
@@ -131,6 +133,13 @@ def lib(path: str | None = None) -> ctypes.CDLL:
             L.nldsc_engine_kept.argtypes = [vp]
             L.nldsc_ld_calculate_keep.argtypes = [ctypes.POINTER(Params), vp, ctypes.c_int32,
                                                   ctypes.POINTER(Result)] + c_err
+        if hasattr(L, "nldsc_engine_run_annot"):
+            L.nldsc_engine_run_annot.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.POINTER(Result), vp, vp] + c_err
+            L.nldsc_ld_calculate_annot.argtypes = [ctypes.POINTER(Params), vp, ctypes.c_int32, vp, ctypes.c_int32,
+                                                   ctypes.POINTER(Result), vp, vp] + c_err
+            L.nldsc_annot_scale_exp.argtypes = [ctypes.c_double]
+            L.nldsc_annot_plan_batches.argtypes = [ctypes.c_int32] * 5 + [vp, ctypes.c_int32]
         L.nldsc_synth_bed_device.argtypes = [ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float,
                                              ctypes.c_uint64] + c_err
@@ -231,3 +240,31 @@ def plan_band(positions, pass_flags, ld_wind, own=None, max_nc=1):
     k2 = lib().nldsc_plan_band(*args, items.ctypes.data, len(items))
     assert k2 == k
     return L_, R_, items[:k]
+
+
+def annot_matrix(annot, n_snp: int) -> np.ndarray:
+    """An [n_snp, C] annotation matrix (a 1-D array is one column) as the C ABI's category-major [C][n_snp] float64
+    array."""
+    a = np.asarray(annot, dtype=np.float64)
+    if a.ndim == 1:
+        a = a[:, None]
+    if a.ndim != 2 or a.shape[0] != n_snp:
+        raise ValueError(f"annot must have shape (n_snp={n_snp}, C), got {a.shape}")
+    return np.ascontiguousarray(a.T)
+
+
+def annot_scale_exp(max_abs: float) -> int:
+    """e_c of an annotation column whose largest |a| is max_abs (C ABI nldsc_annot_scale_exp; host only)."""
+    return int(lib().nldsc_annot_scale_exp(float(max_abs)))
+
+
+def annot_plan_batches(n_items: int, n_it: int, n_cu: int, ksplit_ok: bool = True, batch_items: int = 0) -> np.ndarray:
+    """The batches of an annotated band (C ABI nldsc_annot_plan_batches; host only): rows (first item, items,
+    K-split pieces)."""
+    args = (int(n_items), int(n_it), int(n_cu), int(bool(ksplit_ok)), int(batch_items))
+    k = lib().nldsc_annot_plan_batches(*args, None, 0)
+    if k < 0:
+        raise ValueError(f"nldsc_annot_plan_batches error {k}")
+    out = np.zeros((max(k, 1), 3), np.int32)
+    assert lib().nldsc_annot_plan_batches(*args, out.ctypes.data, len(out)) == k
+    return out[:k]

@@ -221,6 +221,35 @@ SingleShape shape_single(int n_single, int n_it, int n_cu, bool use_f4, int kspl
     return s;
 }
 
+int annot_scale_exp(double max_abs) {
+    if (!(max_abs > 0.0) || !std::isfinite(max_abs)) return 0;
+    int k = 0;
+    const double m = std::frexp(max_abs, &k);  // max_abs = m 2^k, m in [0.5, 1): ceil(log2) is k, or k - 1 at m = 0.5
+    const int e = m == 0.5 ? k - 1 : k;
+    return std::max(0, e);
+}
+
+double annot_scale(int e) { return std::ldexp(1.0, 44 - e); }
+
+int annot_batch_items(int want, size_t cap_bytes) {
+    const size_t hold = std::max<size_t>(1, cap_bytes / ((size_t)ANNOT_KSPLIT_MAX * 32768));
+    const size_t n = want > 0 ? std::min<size_t>((size_t)want, hold) : hold;
+    return (int)std::min<size_t>(n, (size_t)INT32_MAX);
+}
+
+std::vector<AnnotBatch> plan_annot_batches(int n_items, int n_it, int n_cu, bool ksplit_ok, int want,
+                                           size_t cap_bytes) {
+    std::vector<AnnotBatch> out;
+    const int per = annot_batch_items(want, cap_bytes);
+    for (int first = 0; first < n_items; first += per) {
+        const int n = std::min(per, n_items - first);
+        int P = choose_ksplit(n, n_it, n_cu, ksplit_ok);
+        if (P > ANNOT_KSPLIT_MAX) P = ANNOT_KSPLIT_MAX;
+        out.push_back({first, n, P});
+    }
+    return out;
+}
+
 int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it) {
     if (use_t2) return t2_mode == 3 ? NLDSC_BAND_F4_QUAD : t2_mode == 1 ? NLDSC_BAND_F4_ROUTED : NLDSC_BAND_F4_2X2;
     if (path != 2) return path != 0 ? NLDSC_BAND_I8 : NLDSC_BAND_F32;
@@ -244,6 +273,20 @@ int nldsc_plan_band(const double* positions, const uint8_t* flags, int32_t n_snp
         items[4 * k] = it[k].x; items[4 * k + 1] = it[k].y; items[4 * k + 2] = it[k].z; items[4 * k + 3] = 0;
     }
     return (int)it.size();
+}
+
+int nldsc_annot_scale_exp(double max_abs) { return nldsc::annot_scale_exp(max_abs); }
+
+int nldsc_annot_plan_batches(int32_t n_items, int32_t n_it, int32_t n_cu, int32_t ksplit_ok, int32_t batch_items,
+                             int32_t* batches, int32_t cap) {
+    if (n_items < 0 || n_it < 2 || n_cu <= 0 || batch_items < 0) return NLDSC_E_ARG;
+    const std::vector<nldsc::AnnotBatch> b = nldsc::plan_annot_batches(n_items, n_it, n_cu, ksplit_ok != 0, batch_items,
+                                                                       nldsc::ANNOT_GRAM_CAP_BYTES);
+    if ((int64_t)b.size() > (int64_t)cap || !batches) return (int)b.size();
+    for (size_t k = 0; k < b.size(); ++k) {
+        batches[3 * k] = b[k].first; batches[3 * k + 1] = b[k].n; batches[3 * k + 2] = b[k].ksplit;
+    }
+    return (int)b.size();
 }
 
 }  // extern "C"

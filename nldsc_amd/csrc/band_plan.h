@@ -43,6 +43,24 @@ BandChoice choose_band(int n_items, int n_it, int n_cu, bool use_f4, bool ksplit
 struct SingleShape { int round_items, tail_p, n_full; bool defer; };
 SingleShape shape_single(int n_single, int n_it, int n_cu, bool use_f4, int ksplit, bool band_rounds, bool nc2,
                          bool ksplit_ok, bool defer_wanted, size_t rep_gram_max_slots);
+// ---- annotated runs (nldsc_engine_run_annot): fixed-point scale and batches ----
+// Exponent e_c of an annotation column's fixed-point scale 2^(-44 + e_c): max(0, ceil(log2(max_abs))) for the
+// column's largest |a| (finite, >= 0), so |a| <= 2^e_c and a SNP's weighted total (< 2^19 * 2^e_c) fits 63 bits; a
+// 0/1 column keeps the plain scale 2^-44.  annot_scale: the multiplier 2^(44 - e) the kernels apply.
+int annot_scale_exp(double max_abs);
+double annot_scale(int e);
+// Gram scratch of an annotated band: its batches keep batch * P * 32 KiB at or below this (1 GiB)
+constexpr size_t ANNOT_GRAM_CAP_BYTES = (size_t)1 << 30;
+constexpr int ANNOT_KSPLIT_MAX = 8;  // choose_ksplit's largest P
+// Items of one batch: `want` (option "annot_batch_items") when positive, else all the cap holds at P =
+// ANNOT_KSPLIT_MAX; never above that, never below 1.
+int annot_batch_items(int want, size_t cap_bytes);
+// the batches of n_items single-block items, in order: items [first, first + n) K-split in ksplit pieces
+// (choose_ksplit of the batch; the Gram pieces are exact integers, so results do not depend on it)
+struct AnnotBatch { int first, n, ksplit; };
+std::vector<AnnotBatch> plan_annot_batches(int n_items, int n_it, int n_cu, bool ksplit_ok, int want,
+                                           size_t cap_bytes);
+
 // NLDSC_BAND_* (nldsc_ld.h) of a run; path: 0 fp32, 1 int8, 2 fp4; t2_mode: option "t2"
 int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it);
 

@@ -309,6 +309,12 @@ struct nldsc_engine {
     DevBuf<int4> rep_items;
     DevBuf<int> rep_count;
     bool defer_rep = true;
+    // annotated runs (nldsc_engine_run_annot): the annotation matrix, its per-column scales 2^(44 - e_c) and the
+    // per-annotation accumulators (l2c_acc | residual limb, l2dc_acc likewise: [2][n_annot][M] each), category-major;
+    // the finalized owned slice on its way to the host;
+    // option "annot_batch_items" (0: what nldsc::ANNOT_GRAM_CAP_BYTES of Gram scratch holds)
+    DevBuf<double> annot_dev, annot_scale, l2c_acc, l2dc_acc, annot_out;
+    int annot_batch_items = 0;
     // the device table of a run (finish_table's input), kept for a split run between its two calls
     // (nldsc_engine_run_device_split / _finish: `pending`)
     struct SplitState {
@@ -589,6 +595,7 @@ int nldsc_engine_set_option(nldsc_engine* e, const char* name, int64_t value, ch
         {"f4_nc2", 0, 1, [&](int64_t v) { e->f4_nc2 = v != 0; }},
         {"q_rounds", 0, 1, [&](int64_t v) { e->q_rounds = v != 0; }},
         {"defer_rep", 0, 1, [&](int64_t v) { e->defer_rep = v != 0; }},
+        {"annot_batch_items", 0, INT32_MAX, [&](int64_t v) { e->annot_batch_items = (int)v; }},
         {"debug_timing", 0, 1, [&](int64_t v) { e->debug_timing = v != 0; }},
     };
     for (const Opt& o : opts)
@@ -916,7 +923,7 @@ struct PlanMode {
     int route_shift;  // super-items of 2^route_shift blocks a side
 };
 
-PlanMode plan_mode(const nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s) {
+PlanMode plan_mode(const nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, bool annot = false) {
     PlanMode m;
     // band schedule: on the GPU when every position is >= 0 and sorted (the kernels run ahead of the
     // count and the host only waits for two counters), else the host replay of the reference's pointers
@@ -933,6 +940,8 @@ PlanMode plan_mode(const nldsc_engine* e, const nldsc_ld_params* p, const RunSha
     // additive-only fp4 items of two column blocks (GPU plan, unsegmented rows; no K-split: its partial kernel takes
     // single block pairs)
     m.nc2 = e->f4_nc2 && m.gpu_plan && s.use_f4 && !s.dom && s.n_it <= nldsc::F4_SEG_CHUNKS;
+    // annotated runs: single-block items only, whatever the options say (enqueue_band_annot)
+    if (annot) m.t2_cand = m.nc2 = false;
     m.routed = e->t2_mode == 1 || e->t2_mode == 3;
     m.quad = e->t2_mode == 3;
     m.route_shift = m.quad ? 2 : 1;
@@ -1311,11 +1320,111 @@ hipError_t launch_single(nldsc_engine* e, const nldsc::BandArgs& a, const RunSha
     return nldsc::launch_band_f4_split(a, L.shape.tail_p, L.items + n_full, L.n - n_full, e->gram.p, which, L.miss);
 }
 
+// An annotated run's request (nldsc_engine_run_annot): the caller's category-major arrays
+struct AnnotRun {
+    const double* annot;
+    int n;
+    double *l2, *l2d;
+};
+
+// The restrictions of an annotated run, each with its reason, then the annotation matrix and its fixed-point scales
+// to the device (on the main stream, before the prologue) and the accumulators sized.
+int prepare_annot(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const AnnotRun& an, char* err,
+                  size_t errlen) {
+    if (an.n < 1 || an.n > NLDSC_MAX_ANNOT)
+        return set_err(err, errlen, NLDSC_E_ARG, "n_annot %d outside [1, %d]", an.n, NLDSC_MAX_ANNOT);
+    if (!an.annot || !an.l2 || (!an.l2d && s.dom))
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "annot, l2_annot or l2d_annot is NULL (l2d_annot may be NULL only with NLDSC_FLAG_ADDITIVE_ONLY)");
+    if (p->n_org >= (1 << 19))
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "annotated runs need n_org < 2^19 (got %d): the K-split partial kernel takes unsegmented rows",
+                       p->n_org);
+    if (s.path != 2)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "annotated runs take the exact fp4 path only: this run's flags or the band_mode option select %s",
+                       s.path == 0 ? "fp32" : "exact int8");
+    const size_t M = (size_t)s.M, C = (size_t)an.n;
+    std::vector<double> scale(C);
+    for (size_t c = 0; c < C; ++c) {
+        double mx = 0.0;
+        const double* col = an.annot + c * M;
+        for (size_t j = 0; j < M; ++j) {
+            if (!std::isfinite(col[j]))
+                return set_err(err, errlen, NLDSC_E_ARG, "annotation %zu, SNP %zu: the value is not finite", c, j);
+            mx = std::max(mx, std::fabs(col[j]));
+        }
+        scale[c] = nldsc::annot_scale(nldsc::annot_scale_exp(mx));
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(e->annot_dev.ensure(C * M));
+    HIPCHK(e->annot_scale.ensure(C));
+    HIPCHK(e->l2c_acc.ensure(2 * C * M));
+    if (s.dom) HIPCHK(e->l2dc_acc.ensure(2 * C * M));
+    HIPCHK(e->annot_out.ensure(2 * C * (size_t)(s.own_end - s.own_begin)));
+    // (pageable sources: the copies return once the bytes are staged, so `scale` may go out of scope)
+    HIPCHK(hipMemcpyAsync(e->annot_dev.p, an.annot, sizeof(double) * C * M, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->annot_scale.p, scale.data(), sizeof(double) * C, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemsetAsync(e->l2c_acc.p, 0, sizeof(double) * 2 * C * M, e->stream));
+    if (s.dom) HIPCHK(hipMemsetAsync(e->l2dc_acc.p, 0, sizeof(double) * 2 * C * M, e->stream));
+    return NLDSC_OK;
+}
+
+nldsc::AnnotArgs annot_args(const nldsc_engine* e, const RunShape& s, const AnnotRun& an) {
+    const size_t limb = (size_t)an.n * (size_t)s.M;  // (the residual limbs follow the accumulators)
+    return {e->annot_dev.p, e->annot_scale.p, an.n, e->l2c_acc.p, s.dom ? e->l2dc_acc.p : nullptr,
+            e->l2c_acc.p + limb, s.dom ? e->l2dc_acc.p + limb : nullptr};
+}
+
+// The band of an annotated run (ev[3] .. ev[4]): after the rare-variant replay, the single-block items in batches
+// (nldsc::plan_annot_batches) through the K-split partial kernel and the annotated epilogue (launch_band_f4_annot);
+// then the issued-product count as enqueue_band queues it.
+int enqueue_band_annot(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m,
+                       const Schedule& sc, const AnnotRun& an, char* err, size_t errlen) {
+    hipStream_t st = e->stream, cs = e->copy_stream;
+    const int n_items = sc.n_items;
+    HIPCHK(hipEventRecord(e->ev[3], st));
+    const std::vector<nldsc::AnnotBatch> batches = nldsc::plan_annot_batches(
+        n_items, s.n_it, e->n_cu, e->ksplit_ok, e->annot_batch_items, nldsc::ANNOT_GRAM_CAP_BYTES);
+    size_t units = 0;
+    int p_max = 1;
+    for (const nldsc::AnnotBatch& b : batches) {
+        units = std::max(units, (size_t)b.n * (size_t)b.ksplit);
+        p_max = std::max(p_max, b.ksplit);
+    }
+    e->n_band_items = n_items;
+    e->last_ksplit = p_max;
+    e->last_round_items = 0;
+    e->last_tail_ksplit = 1;
+    e->last_band_kernel = NLDSC_BAND_F4_KSPLIT;
+    HIPCHK(e->gram.ensure(std::max<size_t>(units, 1) * 8192));
+    const nldsc::BandArgs a = fill_band_args(e, p, s, m);
+    const nldsc::AnnotArgs aa = annot_args(e, s, an);
+    // the annotated epilogue reads the replayed constants of the KC items: the whole band waits for the replay
+    if (s.replay) HIPCHK(hipStreamWaitEvent(st, e->ev_replay, 0));
+    for (const nldsc::AnnotBatch& b : batches)
+        HIPCHK(nldsc::launch_band_f4_annot(a, aa, b.ksplit, e->items.p + b.first, b.n, e->gram.p));
+    e->last_path = s.path;
+    HIPCHK(hipEventRecord(e->ev[4], st));
+    HIPCHK(e->sums.ensure(3));
+    HIPCHK(e->h_sums.ensure(3 * sizeof(unsigned long long)));
+    HIPCHK(hipStreamWaitEvent(cs, e->ev[3], 0));
+    HIPCHK(hipMemsetAsync(e->sums.p + 2, 0, sizeof(unsigned long long), cs));
+    HIPCHK(nldsc::launch_issued_products(e->items.p, n_items, nullptr, 0, m.gpu_plan ? e->plan_rows.p : nullptr,
+                                         e->blk_miss.p, s.nblk, s.path, s.dom, 0, m.route_shift, e->sums.p + 2, cs));
+    HIPCHK(hipMemcpyAsync(e->h_sums.p + 2 * sizeof(unsigned long long), e->sums.p + 2, sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipEventRecord(e->ev_issued, cs));
+    return NLDSC_OK;
+}
+
 // The band on the main stream (ev[3] .. ev[4]): the super-item launch, the wait for the compacted count, the
 // single-block launches, the KC launches after the replay (ev_replay), or the fp32 launch; then the issued-product
 // count on the side stream (ev_issued).
 int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m, const Schedule& sc,
-                 char* err, size_t errlen) {
+                 char* err, size_t errlen, const AnnotRun* an = nullptr) {
+    if (an) return enqueue_band_annot(e, p, s, m, sc, *an, err, errlen);
     hipStream_t st = e->stream, cs = e->copy_stream;
     const int n_items = sc.n_items;
     HIPCHK(hipEventRecord(e->ev[3], st));
@@ -1475,17 +1584,18 @@ int finish_host(nldsc_engine* e, const RunShape& s, const HostOut& o, double* sw
 // stops before finalize; nldsc_engine_run_device_finish adds the left neighbour's export and finishes.
 int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end, nldsc_ld_result* r,
              double* table_dev, int32_t width, char* err, size_t errlen, long long* export_dev = nullptr,
-             int32_t export_cap = 0, int32_t* export_n = nullptr) {
+             int32_t export_cap = 0, int32_t* export_n = nullptr, const AnnotRun* an = nullptr) {
     const bool split = export_n != nullptr;
     int rc = check_run_args(e, p, own_begin, own_end, r, table_dev, width, split, export_dev, export_cap, err, errlen);
     if (rc) return rc;
+    if (an && (rc = prepare_annot(e, p, run_shape(e, p, own_begin, own_end, split), *an, err, errlen))) return rc;
     if (own_begin == own_end) return run_nothing_owned(e, p->n_snp, own_begin, table_dev, width, err, errlen);
     HIPCHK(hipSetDevice(e->device));
     HostOut out = {};
     e->last_direct = -1;
     if (!table_dev && (rc = resolve_host_out(e, r, own_begin, own_end, &out, err, errlen))) return rc;
     const RunShape s = run_shape(e, p, own_begin, own_end, split);
-    const PlanMode m = plan_mode(e, p, s);
+    const PlanMode m = plan_mode(e, p, s, an != nullptr);
     if ((rc = ensure_run_buffers(e, s, m, err, errlen))) return rc;
 
     const auto t_start = Clock::now();
@@ -1497,7 +1607,13 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     if (rc) return rc;
     // (l2_acc, l2d_acc and ws_acc were zeroed by snp_stats_kernel)
     const auto t_host1 = Clock::now();
-    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen))) return rc;
+    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen, an))) return rc;
+    if (an) {  // the per-annotation scores of the owned slice, finalized beside the ordinary ones (.. ev[5])
+        double* o2 = e->annot_out.p;
+        HIPCHK(nldsc::launch_finalize_annot(e->Lw.p, e->ws_acc.p, annot_args(e, s, *an), s.M, own_begin, own_end, s.dom,
+                                            o2, an->l2d ? o2 + (size_t)an->n * (own_end - own_begin) : nullptr,
+                                            e->stream));
+    }
 
     if (table_dev) e->split = {false, s.M, s.N, s.row_bytes, width, own_begin, own_end, s.dom, table_dev, 0.0};
     if (split) {  // the right halo's sums out; finalize waits for the left neighbour's (run_device_finish)
@@ -1513,6 +1629,14 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     double sw = 0, sd = 0;
     rc = table_dev ? finish_table(e, &sw, &sd, err, errlen) : finish_host(e, s, out, &sw, &sd, err, errlen);
     if (rc) return rc;
+    if (an) {  // (the stream is drained) rows of the owned slice into the caller's [n_annot][M] arrays
+        const size_t n_own = (size_t)(own_end - own_begin), row = sizeof(double) * n_own;
+        HIPCHK(hipMemcpy2D(an->l2 + own_begin, sizeof(double) * (size_t)s.M, e->annot_out.p, row, row, (size_t)an->n,
+                           hipMemcpyDeviceToHost));
+        if (an->l2d)
+            HIPCHK(hipMemcpy2D(an->l2d + own_begin, sizeof(double) * (size_t)s.M, e->annot_out.p + (size_t)an->n * n_own,
+                               row, row, (size_t)an->n, hipMemcpyDeviceToHost));
+    }
     {
         const auto t0 = Clock::now();
         HIPCHK(hipEventSynchronize(e->ev_issued));
@@ -1545,6 +1669,14 @@ int nldsc_engine_run(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begi
                      nldsc_ld_result* r, char* err, size_t errlen) {
     if (!r) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
     return run_impl(e, p, own_begin, own_end, r, nullptr, 0, err, errlen);
+}
+
+int nldsc_engine_run_annot(nldsc_engine* e, const nldsc_ld_params* p, const double* annot, int32_t n_annot,
+                           int32_t own_begin, int32_t own_end, nldsc_ld_result* r, double* l2_annot,
+                           double* l2d_annot, char* err, size_t errlen) {
+    if (!r) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
+    const AnnotRun an = {annot, n_annot, l2_annot, l2d_annot};
+    return run_impl(e, p, own_begin, own_end, r, nullptr, 0, err, errlen, nullptr, 0, nullptr, &an);
 }
 
 int nldsc_engine_run_device(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,
@@ -1634,6 +1766,24 @@ int nldsc_ld_calculate_keep(const nldsc_ld_params* p, const int32_t* idx, int32_
         nldsc_ld_params q = *p;
         q.n_org = e->n_org;  // the kept count (p->n_org without a list)
         rc = nldsc_engine_run(e, &q, 0, p->n_snp, r, err, errlen);
+    }
+    nldsc_engine_destroy(e);
+    return rc;
+}
+
+int nldsc_ld_calculate_annot(const nldsc_ld_params* p, const int32_t* keep_idx, int32_t n_keep, const double* annot,
+                             int32_t n_annot, nldsc_ld_result* r, double* l2_annot, double* l2d_annot, char* err,
+                             size_t errlen) {
+    if (!p || !r || !p->bedfile) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
+    nldsc_engine* e = nullptr;
+    int rc = nldsc_engine_create(p->device, &e, err, errlen);
+    if (rc) return rc;
+    if (keep_idx) rc = nldsc_engine_set_keep(e, keep_idx, n_keep, p->n_org, err, errlen);
+    if (!rc) rc = nldsc_engine_load_bed_file(e, p->bedfile, p->n_snp, p->n_org, err, errlen);
+    if (!rc) {
+        nldsc_ld_params q = *p;
+        q.n_org = e->n_org;  // the kept count (p->n_org without a list)
+        rc = nldsc_engine_run_annot(e, &q, annot, n_annot, 0, p->n_snp, r, l2_annot, l2d_annot, err, errlen);
     }
     nldsc_engine_destroy(e);
     return rc;

@@ -153,6 +153,26 @@ hipError_t launch_band_f4_deferred_epi(const BandArgs& a, int max_items, const D
 // `gram` (n_items * P * 8192 floats), then an epilogue kernel (unsegmented rows, n_it <= F4_SEG_CHUNKS)
 hipError_t launch_band_f4_split(const BandArgs& a, int P, const int4* items, int n_items, float* gram, int which,
                                 const uint8_t* blk_miss);
+// Partitioned LD scores (nldsc_engine_run_annot): the annotation matrix and its accumulators, category-major
+// [n_annot][n_snp] in device memory.  ascale[c] = 2^(44 - e_c) (band_plan.h annot_scale_exp): the accumulators hold
+// the weighted sums in units of 1 / ascale[c] as 64-bit integers, l2c_lo / l2dc_lo what that rounding dropped of each
+// item's partial in units of 2^-40 of those (all zeroed before the band); l2dc_acc, l2dc_lo nullptr: additive only
+struct AnnotArgs {
+    const double* annot;
+    const double* ascale;
+    int n_annot;
+    double *l2c_acc, *l2dc_acc, *l2c_lo, *l2dc_lo;
+};
+// one batch of an annotated band: band_f4_part_kernel (P pieces per item, all items) into `gram` (n_items * P * 8192
+// floats), then band_f4_epi_annot_kernel — the ordinary per-SNP sums as band_f4_epi_kernel adds them plus the
+// per-annotation sums — for the items without a replayed SNP and, with a.blk_rep, its KC instantiation for the
+// others (the caller has waited for the replay).  Single-block items (I, J, 1, 0), unsegmented rows, no routing.
+hipError_t launch_band_f4_annot(const BandArgs& a, const AnnotArgs& an, int P, const int4* items, int n_items,
+                                float* gram);
+// L2[j, c] = a[j, c] + sum, L2D[j, c] = sum of the owned slice to out_l2 / out_l2d ([n_annot][own_hi - own_lo],
+// device memory; out_l2d may be nullptr), NaN where the plain L2 / L2D are (and L2D everywhere without dom)
+hipError_t launch_finalize_annot(const int* Lw, const int* ws_acc, const AnnotArgs& an, int n_snp, int own_lo,
+                                 int own_hi, bool dom, double* out_l2, double* out_l2d, hipStream_t st);
 // 2 x 2 block-pair workgroups (unsegmented rows, gpu plan): super-items (I2, J2, 1, 0) over row / column
 // super-blocks of two 32-SNP blocks, planned from the single-block rows (launch_plan) by launch_plan_super (meta2
 // as meta; counts2 capacity ceil(nblk2/16)^2) and launch_plan_emit_super; the kernel reads `rows` (nblk) to skip the

@@ -2852,6 +2852,249 @@ __global__ void __launch_bounds__(64, 2) band_f4_epi_kernel(const SnpConst* __re
                                           l2d_acc, ws_acc);
 }
 
+// ---- partitioned LD scores: L2[j, c] = sum_k a[k, c] r2adj(j, k) per annotation column c (and the dominance sum) ----
+// An annotated run sends every block pair through band_f4_part_kernel (exact Gram tiles to memory) and then through
+// band_f4_epi_annot_kernel, which is band_f4_epi_kernel plus the per-annotation sums: the pair loop below is
+// pair_epilogue<DOM, f32x16v, true, KC> expression for expression (the seven ordinary arrays are bitwise those of a
+// plain run) and keeps each pair's masked r2 values in an LDS tile; the annotations then go by in chunks of
+// ANNOT_CHUNK columns whose weights for the item's 64 slots are staged through LDS, each column's four weighted sums
+// reduced with reduce_rows4 / xlane in the plain epilogue's order and added to category-major fixed-point
+// accumulators acc[c * n_snp + g] in units of 1 / ascale[c] (= 2^(-44 + e_c), band_plan.h annot_scale_exp: a SNP's
+// total stays below 2^63 for |a| <= 2^e_c) with 64-bit integer atomics: order-independent, bit-reproducible.  What
+// that rounding drops of an item's partial goes, in units of 2^-40 of the first, to a second accumulator of the same
+// layout (|residual| <= 2^39 per item, fewer than 2^20 items per SNP), so a total carries the fp64 partials'
+// own precision: a column and a multiple of it then agree to the rounding of their fp64 products, whatever e_c.
+constexpr int ANNOT_CHUNK = 16;
+constexpr double ANNOT_LO_SCALE = 1099511627776.0;  // 2^40
+
+struct AnnotSlots {
+    SnpSlot info[64];
+    SnpConst cst[64];
+};
+
+// One slot's weighted sum of one work item and one annotation -> that annotation's per-SNP total.  Exact zeros (an
+// annotation without a member among the other block's SNPs: binary annotations are mostly zero) add nothing; a
+// non-finite sum (a window poisoned by an all-missing SNP: 0 * NaN is NaN too) never reaches the integer conversion —
+// the plain sums of the same slot set the nanf bit finalize reads for every annotation.
+__device__ __forceinline__ void flush_annot(int g, double v, double scale, int own_lo, int own_hi, int n_snp,
+                                            double* acc, double* acc_lo) {
+    if (v == 0.0 || !isfinite(v) || g < own_lo || g >= own_hi || g >= n_snp) return;
+    const double s = v * scale;  // (a power of two: exact)
+    const long long hi = __double2ll_rn(s);
+    const long long lo = __double2ll_rn((s - (double)hi) * ANNOT_LO_SCALE);  // (the difference is exact, <= 1/2)
+    atomicAdd(reinterpret_cast<unsigned long long*>(&acc[g]), (unsigned long long)hi);
+    if (lo != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&acc_lo[g]), (unsigned long long)lo);
+}
+
+// (no waves-per-SIMD bound: the 37 / 53 KiB of LDS hold the kernel to 4 / 3 workgroups per CU, and the plain
+// epilogue's registers beside the kept r2 values need more than the 256 a second wave per SIMD would leave)
+template <bool DOM, bool KC>
+__global__ void __launch_bounds__(64) band_f4_epi_annot_kernel(
+    const SnpConst* __restrict__ cst, const int4* __restrict__ items, const double* __restrict__ pos,
+    const int* __restrict__ Lw, const int* __restrict__ Rw, const uint8_t* __restrict__ sflags, int n_snp,
+    double ld_wind, double n_org, double rsq_thr, int own_lo, int own_hi, double* __restrict__ l2_acc,
+    double* __restrict__ l2d_acc, int* __restrict__ ws_acc, const uint8_t* __restrict__ blk_rep, int P,
+    const float* __restrict__ gram, const double* __restrict__ annot, const double* __restrict__ ascale, int n_annot,
+    double* __restrict__ l2c_acc, double* __restrict__ l2dc_acc, double* __restrict__ l2c_lo,
+    double* __restrict__ l2dc_lo) {
+    __shared__ AnnotSlots sh;
+    __shared__ float tr[32 * 33];
+    // masked r2 of the lane's 16 pairs: [0] nij ? r2 : 0 (row SNP's additive term), [1] nji ? r2 : 0 (column SNP's),
+    // [2], [3] the dominance terms of the row / column SNP; each lane reads back only what it wrote
+    __shared__ double pv[DOM ? 4 : 2][16][64];
+    __shared__ double wt[ANNOT_CHUNK][64];  // a chunk's weights of the 64 slots
+    const int4 it = items[blockIdx.x];
+    if (skip_item<KC>(blk_rep, it)) return;
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int I = it.x, J = it.y;
+    const bool diag = I == J;
+    {
+        const int s = lane;
+        const int g = s < 32 ? I * 32 + s : J * 32 + (s & 31);
+        SnpSlot si;
+        si.g = g;
+        if (g < n_snp) {
+            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
+        } else {
+            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
+        }
+        sh.info[s] = si;
+        sh.cst[s] = cst[g];
+    }
+    f32x16v g8[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) g8[t] = f32x16v{};
+    const float* src = gram + (size_t)blockIdx.x * P * 8192 + lane * 16;
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const float4* q = reinterpret_cast<const float4*>(src + (size_t)p * 8192 + t * 1024);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 v = q[k];
+                g8[t][4 * k] += v.x; g8[t][4 * k + 1] += v.y; g8[t][4 * k + 2] += v.z; g8[t][4 * k + 3] += v.w;
+            }
+        }
+    __syncthreads();
+    if (diag) {  // m.x(a, b) = x.m(b, a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = g8[1][r];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) g8[2][r] = tr[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
+    }
+    // ---- the plain epilogue (pair_epilogue, MB basis), each pair's r2 values kept ----
+    const SnpSlot* info = sh.info;
+    const f32x16v &gxx = g8[0], &gxo = g8[1], &gox = g8[2], &goo = g8[3], &gxh = g8[4], &goh = g8[5], &ghx = g8[6],
+                  &gho = g8[7];
+    const double kslots = n_org;
+    const R2Adj r2adj(n_org);
+    const int sj = 32 + i;
+    const SnpSlot cj = info[sj];
+    {
+        const SnpConst kj = sh.cst[sj];
+        const bool rpj = (cj.fl & 2) != 0;
+        SlotSum col = {0.0, 0.0, 0}, mine = {0.0, 0.0, 0};
+        int my_row = -1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {  // row group q: registers r = 4q + k, rows k + 8q + 4h
+            SlotSum rowv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int r = 4 * q + k;
+                const int si = k + 8 * q + 4 * h;
+                const SnpSlot ci = info[si];
+                const bool rpi = (ci.fl & 2) != 0;
+                const PairNeed need = pair_need(ci, cj, diag, ld_wind);
+                const bool nij = need.nij, nji = need.nji;
+                SlotSum rv = {0.0, 0.0, 0};
+                double p_row = 0.0, p_col = 0.0, d_row = 0.0, d_col = 0.0;
+                if (nij || nji) {
+                    const SnpConst ki = sh.cst[si];
+                    const double mm = (double)goo[r];
+                    const double xx = 0.25 * ((double)gxx[r] - (double)gxo[r] - (double)gox[r] + mm);
+                    const double xo = ki.X - 0.5 * ((double)gxo[r] - mm);
+                    const double ox = kj.X - 0.5 * ((double)gox[r] - mm);
+                    const double oo = ki.Ob + kj.Ob - kslots + mm;
+                    const double aa = (xx - kj.mu * xo - ki.mu * (ox - kj.mu * oo)) * (ki.isa * kj.isa) +
+                                      (KC ? kj.ka * ki.SA + ki.ka * (kj.SA + kj.ka * n_org) : 0.0);
+                    const double r2 = r2adj(aa);
+                    if (nij) { rv.l2 = r2; rv.cnt = 1; p_row = r2; }
+                    if (nji) { col.l2 += r2; col.cnt += 1; p_col = r2; }
+                    if (DOM) {
+                        if (nij && rpj) {  // A_i . R_j -> L2D_i
+                            const double xh = 0.5 * ((double)gxh[r] - (double)goh[r]);
+                            const double oh = kj.H - (double)goh[r];
+                            const double ar = (2.0 * xh - kj.beta * xx - kj.c * xo -
+                                               ki.mu * (2.0 * oh - kj.beta * ox - kj.c * oo)) * (ki.isa * kj.is) +
+                                              (KC ? kj.kr * ki.SA + ki.ka * (kj.SR + kj.kr * n_org) : 0.0);
+                            const double rd = r2adj(ar);
+                            rv.l2d = rd;
+                            rv.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
+                            d_row = rd;
+                        }
+                        if (!diag && nji && rpi) {  // R_i . A_j -> L2D_j
+                            const double hx = 0.5 * ((double)ghx[r] - (double)gho[r]);
+                            const double ho = ki.H - (double)gho[r];
+                            const double ra = (2.0 * hx - ki.beta * xx - ki.c * ox -
+                                               kj.mu * (2.0 * ho - ki.beta * xo - ki.c * oo)) * (ki.is * kj.isa) +
+                                              (KC ? ki.kr * kj.SA + kj.ka * (ki.SR + ki.kr * n_org) : 0.0);
+                            const double rd = r2adj(ra);
+                            col.l2d += rd;
+                            col.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
+                            d_col = rd;
+                        }
+                    }
+                }
+                rowv[k] = rv;
+                pv[0][r][lane] = p_row;
+                pv[1][r][lane] = p_col;
+                if (DOM) {
+                    pv[2][r][lane] = d_row;
+                    pv[3][r][lane] = d_col;
+                }
+            }
+            const SlotSum t = reduce_rows4(rowv, i);  // lanes i >> 3 == k: row k + 8q + 4h
+            if ((i & 7) == q) {
+                mine = t;
+                my_row = (i >> 3) + 8 * q + 4 * h;
+            }
+        }
+        col = col + xlane<32>(col);  // the partner lane (i, 1 - h) holds the other 16 rows of column i
+        if (my_row >= 0) flush_slot(info[my_row], mine, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
+        if (h == 0) flush_slot(cj, col, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
+    }
+    // ---- the per-annotation sums: the same four sums, each pair weighted by the other SNP's annotation value ----
+    const int my_q = i & 7;  // lanes with my_q < 4 end reduce_rows4 of row group my_q with a row's total
+    const int g_row = my_q < 4 ? info[(i >> 3) + 8 * my_q + 4 * h].g : n_snp;
+    for (int c0 = 0; c0 < n_annot; c0 += ANNOT_CHUNK) {
+        const int nc = min(ANNOT_CHUNK, n_annot - c0);
+        __syncthreads();  // (the chunk before is read)
+        {
+            const int g = info[lane].g;
+            for (int cc = 0; cc < nc; ++cc)
+                wt[cc][lane] = g < n_snp ? annot[(size_t)(c0 + cc) * n_snp + g] : 0.0;
+        }
+        __syncthreads();
+        for (int cc = 0; cc < nc; ++cc) {
+            const size_t cbase = (size_t)(c0 + cc) * n_snp;
+            const double scale = ascale[c0 + cc];
+            const double aj = wt[cc][sj];
+            SlotSum col = {0.0, 0.0, 0}, mine = {0.0, 0.0, 0};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                SlotSum rowv[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int r = 4 * q + k;
+                    const double ai = wt[cc][k + 8 * q + 4 * h];
+                    rowv[k] = SlotSum{pv[0][r][lane] * aj, DOM ? pv[2][r][lane] * aj : 0.0, 0};
+                    col.l2 += pv[1][r][lane] * ai;
+                    if (DOM) col.l2d += pv[3][r][lane] * ai;
+                }
+                const SlotSum t = reduce_rows4(rowv, i);
+                if (my_q == q) mine = t;
+            }
+            col = col + xlane<32>(col);
+            flush_annot(g_row, mine.l2, scale, own_lo, own_hi, n_snp, l2c_acc + cbase, l2c_lo + cbase);
+            if (h == 0) flush_annot(cj.g, col.l2, scale, own_lo, own_hi, n_snp, l2c_acc + cbase, l2c_lo + cbase);
+            if (DOM) {
+                flush_annot(g_row, mine.l2d, scale, own_lo, own_hi, n_snp, l2dc_acc + cbase, l2dc_lo + cbase);
+                if (h == 0)
+                    flush_annot(cj.g, col.l2d, scale, own_lo, own_hi, n_snp, l2dc_acc + cbase, l2dc_lo + cbase);
+            }
+        }
+    }
+}
+
+// finalize of the per-annotation sums (finalize_kernel's rules): computed SNPs get a[j, c] * 1 + sum — the self
+// term, as L2's 1 + — and the dominance sum as it stands, NaN where the plain L2 / L2D are NaN (the same nanf bits);
+// SNPs that are not computed get NaN.  out_l2 / out_l2d: [n_annot][own_hi - own_lo].
+__global__ void __launch_bounds__(256) finalize_annot_kernel(
+    const int* __restrict__ Lw, const int* __restrict__ ws_acc, const double* __restrict__ l2c_acc,
+    const double* __restrict__ l2dc_acc, const double* __restrict__ l2c_lo, const double* __restrict__ l2dc_lo,
+    const double* __restrict__ annot, const double* __restrict__ ascale, int n_snp, int own_lo, int own_hi, int dom,
+    double* __restrict__ out_l2, double* __restrict__ out_l2d) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, g = own_lo + k, c = blockIdx.y;
+    if (g >= own_hi) return;
+    const double qnan = __builtin_nan("");
+    double a2 = qnan, d2 = qnan;
+    if (Lw[g] >= 0) {
+        const int nanf = ws_acc[3 * (size_t)n_snp + g];
+        const size_t at = (size_t)c * n_snp + g;
+        const double s = ascale[c];
+        auto total = [&](const double* hi, const double* lo) {
+            return ((double)reinterpret_cast<const long long*>(hi)[at] +
+                    (double)reinterpret_cast<const long long*>(lo)[at] / ANNOT_LO_SCALE) / s;
+        };
+        if (!(nanf & 1)) a2 = annot[at] * 1.0 + total(l2c_acc, l2c_lo);
+        if (dom && !(nanf & 2)) d2 = total(l2dc_acc, l2dc_lo);
+    }
+    const size_t o = (size_t)c * (own_hi - own_lo) + k;
+    out_l2[o] = a2;
+    if (out_l2d != nullptr) out_l2d[o] = d2;
+}
+
 // ------------------------------------------------------------------------------------------
 // 4. finalize
 // ------------------------------------------------------------------------------------------
@@ -3309,6 +3552,35 @@ hipError_t launch_band_f4_split(const BandArgs& a, int P, const int4* items, int
 kc:
     if (a.blk_rep && (which & 2)) { if (a.dom) NLDSC_EPI(true, true); else NLDSC_EPI(false, true); }
 #undef NLDSC_EPI
+    return hipGetLastError();
+}
+
+hipError_t launch_band_f4_annot(const BandArgs& a, const AnnotArgs& an, int P, const int4* items, int n_items,
+                                float* gram) {
+    if (n_items <= 0) return hipSuccess;
+    if (a.n_it > F4_SEG_CHUNKS || P < 1 || 2 * P > a.n_it || an.n_annot < 1) return hipErrorInvalidValue;
+    const dim3 grid_p((unsigned)n_items * (unsigned)P);
+    if (a.dom) hipLaunchKernelGGL((band_f4_part_kernel<true>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS,
+                                  P, gram, nullptr, a.route_shift);
+    else hipLaunchKernelGGL((band_f4_part_kernel<false>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS, P,
+                            gram, nullptr, a.route_shift);
+#define NLDSC_EPI(DOM_, KC_)                                                                                        \
+    hipLaunchKernelGGL((band_f4_epi_annot_kernel<DOM_, KC_>), dim3(n_items), dim3(64), 0, a.st, a.cst, items,      \
+                       A_SNPS, A_EPI, a.blk_rep, P, gram, an.annot, an.ascale, an.n_annot, an.l2c_acc, an.l2dc_acc,   \
+                       an.l2c_lo, an.l2dc_lo)
+    if (a.dom) NLDSC_EPI(true, false); else NLDSC_EPI(false, false);
+    if (a.blk_rep) { if (a.dom) NLDSC_EPI(true, true); else NLDSC_EPI(false, true); }
+#undef NLDSC_EPI
+    return hipGetLastError();
+}
+
+hipError_t launch_finalize_annot(const int* Lw, const int* ws_acc, const AnnotArgs& an, int n_snp, int own_lo,
+                                 int own_hi, bool dom, double* out_l2, double* out_l2d, hipStream_t st) {
+    const int n = own_hi - own_lo;
+    if (n <= 0 || an.n_annot <= 0) return hipSuccess;
+    hipLaunchKernelGGL(finalize_annot_kernel, dim3((n + 255) / 256, an.n_annot), dim3(256), 0, st, Lw, ws_acc,
+                       an.l2c_acc, an.l2dc_acc, an.l2c_lo, an.l2dc_lo, an.annot, an.ascale, n_snp, own_lo, own_hi,
+                       dom ? 1 : 0, out_l2, out_l2d);
     return hipGetLastError();
 }
 

@@ -7,10 +7,12 @@
 // `calculate` raises RuntimeError.
 //
 // Differences from the reference, all additive: the GIL is released during `calculate`;
-// LDScoreParams has three extra attributes, `flags` (NLDSC_FLAG_*), `device` (HIP ordinal,
-// default from $NLDSC_DEVICE, else the current device) and `keep` (0-based .fam line numbers of the
-// individuals to use, strictly ascending; empty: everyone — nldsc_ld_calculate_keep); errors carry
-// the engine's message.
+// LDScoreParams has four extra attributes, `flags` (NLDSC_FLAG_*), `device` (HIP ordinal,
+// default from $NLDSC_DEVICE, else the current device), `keep` (0-based .fam line numbers of the
+// individuals to use, strictly ascending; empty: everyone — nldsc_ld_calculate_keep) and `annot` (an
+// annotation matrix, row-major [n_snp][n_annot]; empty: none — nldsc_ld_calculate_annot), and
+// LDScoreResult two, `l2_annot` and `l2d_annot` (row-major [n_snp][n_annot], empty without `annot`);
+// errors carry the engine's message.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -37,6 +39,7 @@ struct LDScoreParams {  // data.h:33-65
     unsigned flags = 0;
     int device = -1;
     std::vector<int> keep;  // .fam lines of the individuals to use (empty: everyone); n_org stays the file's count
+    std::vector<double> annot;  // annotation matrix, row-major [n_snp][n_annot] (empty: none)
 
     LDScoreParams() {
         if (const char* d = std::getenv("NLDSC_DEVICE")) device = std::atoi(d);
@@ -58,6 +61,7 @@ struct LDScoreParams {  // data.h:33-65
 struct LDScoreResult {  // data.h:21-31
     std::vector<double> l2, l2d, maf, residuals_std;
     std::vector<int> l2_ws, l2d_ws, l2d_wse;
+    std::vector<double> l2_annot, l2d_annot;  // row-major [n_snp][n_annot]; empty without LDScoreParams::annot
 };
 
 LDScoreResult calculate(const LDScoreParams& params) {
@@ -88,7 +92,31 @@ LDScoreResult calculate(const LDScoreParams& params) {
                       reinterpret_cast<int32_t*>(res.l2d_wse.data())};
     char err[1024] = {0};
     int rc;
-    {
+    if (!params.annot.empty()) {
+        if (n == 0 || params.annot.size() % n != 0)
+            throw std::invalid_argument("annot must have n_snp * n_annot elements");
+        const size_t C = params.annot.size() / n;
+        // the C ABI takes and fills category-major [n_annot][n_snp] arrays
+        std::vector<double> a(C * n), l2c(C * n), l2dc(C * n);
+        for (size_t j = 0; j < n; ++j)
+            for (size_t c = 0; c < C; ++c) a[c * n + j] = params.annot[j * C + c];
+        {
+            py::gil_scoped_release nogil;
+            rc = nldsc_ld_calculate_annot(&p, params.keep.empty() ? nullptr
+                                                                  : reinterpret_cast<const int32_t*>(params.keep.data()),
+                                          (int32_t)params.keep.size(), a.data(), (int32_t)C, &r, l2c.data(), l2dc.data(),
+                                          err, sizeof(err));
+        }
+        if (rc == NLDSC_OK) {
+            res.l2_annot.resize(C * n);
+            res.l2d_annot.resize(C * n);
+            for (size_t j = 0; j < n; ++j)
+                for (size_t c = 0; c < C; ++c) {
+                    res.l2_annot[j * C + c] = l2c[c * n + j];
+                    res.l2d_annot[j * C + c] = l2dc[c * n + j];
+                }
+        }
+    } else {
         py::gil_scoped_release nogil;
         rc = params.keep.empty() ? nldsc_ld_calculate(&p, &r, err, sizeof(err))
                                  : nldsc_ld_calculate_keep(&p, reinterpret_cast<const int32_t*>(params.keep.data()),
@@ -118,7 +146,8 @@ PYBIND11_MODULE(_ldscore, m) {
         .def_readwrite("rsq_thr", &LDScoreParams::rsq_thr)
         .def_readwrite("flags", &LDScoreParams::flags)
         .def_readwrite("device", &LDScoreParams::device)
-        .def_readwrite("keep", &LDScoreParams::keep);
+        .def_readwrite("keep", &LDScoreParams::keep)
+        .def_readwrite("annot", &LDScoreParams::annot);
 
     py::class_<LDScoreResult> R(m, "LDScoreResult");
     R.def(py::init());
@@ -128,7 +157,9 @@ PYBIND11_MODULE(_ldscore, m) {
         .def_readwrite("residuals_std", &LDScoreResult::residuals_std)
         .def_readwrite("l2_ws", &LDScoreResult::l2_ws)
         .def_readwrite("l2d_ws", &LDScoreResult::l2d_ws)
-        .def_readwrite("l2d_wse", &LDScoreResult::l2d_wse);
+        .def_readwrite("l2d_wse", &LDScoreResult::l2d_wse)
+        .def_readwrite("l2_annot", &LDScoreResult::l2_annot)
+        .def_readwrite("l2d_annot", &LDScoreResult::l2d_annot);
 
     m.def("calculate", &calculate);
     m.attr("__version__") = nldsc_version();

@@ -118,9 +118,11 @@ class Engine:
         self._loaded(n_snp, n_org)
 
     # ---- compute ------------------------------------------------------------------------
-    def run(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, out=None):
+    def run(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, out=None, annot=None):
         """LD scores for owned SNPs [own[0], own[1]) (default all).  Returns dict of numpy arrays
-        (entries outside the owned range are NaN / -1, or whatever `out` held)."""
+        (entries outside the owned range are NaN / -1, or whatever `out` held).  `annot`: an [n_snp, C] annotation
+        matrix (C ABI nldsc_engine_run_annot); the dict then also holds "l2_annot" and "l2d_annot", [n_snp, C]
+        float64 (taken from `out` when it has them, category-major [C, n_snp] contiguous arrays viewed transposed)."""
         n = self.n_snp
         own = (0, n) if own is None else own
         p, _keep = _lib.make_params(n, self.n_org, ld_wind, maf, std_thr, rsq_thr, positions, flags=flags)
@@ -132,6 +134,17 @@ class Engine:
             res = _lib.Result(*(arrs[k].ctypes.data_as(d if arrs[k].dtype == np.float64 else i)
                                 for k in ("l2", "l2d", "maf", "residuals_std", "l2_ws", "l2d_ws", "l2d_wse")))
         err = _lib.errbuf()
+        if annot is not None:
+            a = _lib.annot_matrix(annot, n)
+            for k in ("l2_annot", "l2d_annot"):
+                if k not in arrs:
+                    arrs[k] = np.full((a.shape[0], n), np.nan).T
+                if arrs[k].T.shape != a.shape or not arrs[k].T.flags.c_contiguous or arrs[k].dtype != np.float64:
+                    raise ValueError(f"out['{k}'] must be the transposed view of a contiguous float64 [C, n_snp] array")
+            _lib.check(self._L.nldsc_engine_run_annot(self._h, ctypes.byref(p), a.ctypes.data, a.shape[0], int(own[0]),
+                                                      int(own[1]), ctypes.byref(res), arrs["l2_annot"].T.ctypes.data,
+                                                      arrs["l2d_annot"].T.ctypes.data, err, len(err)), err)
+            return arrs
         _lib.check(self._L.nldsc_engine_run(self._h, ctypes.byref(p), int(own[0]), int(own[1]),
                                                ctypes.byref(res), err, len(err)), err)
         return arrs
@@ -209,13 +222,24 @@ class Engine:
 
 
 def calculate(bedfile: str, n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, *, flags=0, device=-1,
-              keep=None) -> dict:
+              keep=None, annot=None) -> dict:
     """One-shot C-ABI call `nldsc_ld_calculate` (file -> GPU -> results); with `keep` (0-based .fam line numbers,
-    strictly ascending; n_org stays the file's count) `nldsc_ld_calculate_keep`, on those individuals only."""
+    strictly ascending; n_org stays the file's count) `nldsc_ld_calculate_keep`, on those individuals only; with
+    `annot` ([n_snp, C]) `nldsc_ld_calculate_annot`, which adds "l2_annot" and "l2d_annot" ([n_snp, C])."""
     p, _pos = _lib.make_params(n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, bedfile=bedfile,
                                flags=flags, device=device)
     arrs, res = _lib.alloc_result(n_snp)
     err = _lib.errbuf()
+    if annot is not None:
+        a = _lib.annot_matrix(annot, n_snp)
+        idx = None if keep is None or len(keep) == 0 else np.ascontiguousarray(keep, dtype=np.int32)
+        for k in ("l2_annot", "l2d_annot"):
+            arrs[k] = np.full((a.shape[0], n_snp), np.nan).T
+        _lib.check(_lib.lib().nldsc_ld_calculate_annot(
+            ctypes.byref(p), None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx), a.ctypes.data,
+            a.shape[0], ctypes.byref(res), arrs["l2_annot"].T.ctypes.data, arrs["l2d_annot"].T.ctypes.data, err,
+            len(err)), err)
+        return arrs
     if keep is None or len(keep) == 0:
         _lib.check(_lib.lib().nldsc_ld_calculate(ctypes.byref(p), ctypes.byref(res), err, len(err)), err)
     else:

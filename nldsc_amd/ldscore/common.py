@@ -6,6 +6,7 @@ The reference's public names, validation rules and messages, 
   BIMFile / FAMFile      tab-separated tables, one chromosome per .bim; n_snp / n_org = number of lines
   read_id_file, kept_individuals   --keep / --remove lists (FID IID per line) -> .fam line numbers (no reference
                          counterpart: PLINK's / LDSC's flags of the same names)
+  AnnotFile              LDSC's .annot / .annot.gz (partitioned LD scores, --annot): names + an [M, C] float64 matrix
   MAF, ResidualsSTDThreshold, RSQThreshold: [0, 1), [0, 1), [0, 0.1)
 (RSQThreshold's repr says `std_thr=`, as the reference's does.)
 """
@@ -21,7 +22,7 @@ from ..core.common import Data, NLDSCParameterError
 from ..core.logger import log
 
 __all__ = ["LDWindow", "PLINKFile", "BEDFile", "BIMFile", "FAMFile", "MAF", "ResidualsSTDThreshold",
-           "RSQThreshold", "NLDSCParameterError", "read_id_file", "kept_individuals"]
+           "RSQThreshold", "NLDSCParameterError", "read_id_file", "kept_individuals", "AnnotFile"]
 
 # window metric -> (largest window, how the message names it)
 _WINDOW_LIMITS = {"bp": (5 * 10 ** 6, "5 Mbp"), "cm": (100, "100 cm")}
@@ -161,6 +162,78 @@ class FAMFile(PLINKFile):
 
     def __repr__(self):
         return f"FAMFile(n_org={self.n_org})"
+
+
+class AnnotFile(Data):
+    """LDSC's annotation file (`.annot`, or `.annot.gz`): whitespace-delimited with a header line.  The full form
+    leads with the columns CHR BP SNP CM and its SNP column must equal the .bim's, row for row; the thin form holds
+    annotation columns only and must have one row per .bim SNP.  `names`: the annotation columns' names (no
+    duplicates); `data`: their values, an [M, C] float64 matrix, every one numeric and finite."""
+    LEAD = ("CHR", "BP", "SNP", "CM")
+
+    def __init__(self, path: str, bim: BIMFile):
+        import gzip
+        self._path = str(path)
+        if not os.path.exists(self._path):
+            raise FileNotFoundError(f'No such file: "{self._path}"')
+        opener = gzip.open if self._path.endswith(".gz") else open
+        with opener(self._path, "rt") as fh:
+            header = fh.readline().split()
+            rows = [f for f in (line.split() for line in fh) if f]
+        self._full = tuple(header[:4]) == self.LEAD
+        self._names = header[4:] if self._full else header
+        self._rows, self._bim = rows, bim
+        self._validate()
+        del self._rows, self._bim
+
+    @property
+    def names(self) -> list:
+        return list(self._names)
+
+    def __repr__(self):
+        return f"AnnotFile(path='{self._path}', n_annot={len(self._names)})"
+
+    def _validate(self):
+        where = f'"{self._path}"'
+        if not self._names:
+            raise NLDSCParameterError(f"{where}: no annotation column")
+        dup = sorted({n for n in self._names if self._names.count(n) > 1})
+        if dup:
+            raise NLDSCParameterError(f"{where}: duplicate annotation column name {dup[0]}")
+        lead = 4 if self._full else 0
+        width = lead + len(self._names)
+        m = self._bim.n_snp
+        if len(self._rows) != m:
+            raise NLDSCParameterError(f"{where}: {len(self._rows)} rows, but the .bim has {m} SNPs")
+        for k, f in enumerate(self._rows):
+            if len(f) != width:
+                raise NLDSCParameterError(f"{where}, row {k + 1}: {len(f)} fields, expected {width}")
+        if self._full:
+            snp = [str(s) for s in self._bim.snp.tolist()]
+            for k, f in enumerate(self._rows):
+                if f[2] != snp[k]:
+                    raise NLDSCParameterError(f"{where}, row {k + 1}: SNP {f[2]} where the .bim has {snp[k]}: the "
+                                              f"annotation rows must be the .bim's, in its order")
+        data = np.empty((m, len(self._names)), dtype=np.float64)
+        for k, f in enumerate(self._rows):
+            try:
+                data[k] = [float(v) for v in f[lead:]]
+            except ValueError:
+                bad = next(v for v in f[lead:] if not _is_number(v))
+                raise NLDSCParameterError(f"{where}, row {k + 1}: non-numeric value {bad!r}") from None
+        bad = np.argwhere(~np.isfinite(data))
+        if len(bad):
+            k, c = bad[0]
+            raise NLDSCParameterError(f"{where}, row {k + 1}, column {self._names[c]}: the value is not finite")
+        self._data = data
+
+
+def _is_number(text: str) -> bool:
+    try:
+        float(text)
+        return True
+    except ValueError:
+        return False
 
 
 def _threshold(name: str, field: str, hi: float, message: str):

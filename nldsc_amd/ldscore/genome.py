@@ -18,8 +18,10 @@ import numpy as np
 
 from ..core.common import NLDSCParameterError, elapsed_time
 from ..core.logger import log
-from .common import FAMFile, BIMFile, LDWindow, MAF, ResidualsSTDThreshold, RSQThreshold, kept_individuals
-from .routine import m_values, make_output, write_m_file, write_scores
+from .common import (AnnotFile, FAMFile, BIMFile, LDWindow, MAF, ResidualsSTDThreshold, RSQThreshold,
+                     kept_individuals)
+from .routine import (annot_output, m_annot_values, m_values, make_output, reject_sharded_annot, write_m_annot_file,
+                      write_m_file, write_scores)
 
 CHROMS = [str(c) for c in range(1, 23)] + ["X", "Y", "XY", "MT"]
 
@@ -81,9 +83,9 @@ def _default_runner(device: int, keep=None, n_org_file: int = 0):
     if keep is not None:
         eng.set_keep(keep, n_org_file)
 
-    def run(bed_path: str, n_snp: int, n_org: int, ld_wind, maf, std_thr, rsq_thr, positions, flags):
+    def run(bed_path: str, n_snp: int, n_org: int, ld_wind, maf, std_thr, rsq_thr, positions, flags, annot=None):
         eng.load_bed_file(bed_path, n_snp, n_org)
-        return eng.run(ld_wind, maf, std_thr, rsq_thr, positions, flags=flags), eng.timings()
+        return eng.run(ld_wind, maf, std_thr, rsq_thr, positions, flags=flags, annot=annot), eng.timings()
     run.wants_path = True
     return run
 
@@ -94,10 +96,16 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
                         extra: bool = False, write_m: bool = False, flags: int = 0, device: int | None = None,
                         runner=None, rank: int | None = None, world: int | None = None,
                         progress: bool | None = None, keep: str | None = None,
-                        remove: str | None = None) -> dict:
+                        remove: str | None = None, annot: str | None = None) -> dict:
     """Returns {chromosome: output DataFrame (None when written to `out`)} for the chromosomes this rank
     processed.  `keep` / `remove`: `FID IID` lists as in estimate_lds; every chromosome's .fam must resolve to the
-    same individuals (a `runner` given by the caller then receives them as the keyword `keep`)."""
+    same individuals (a `runner` given by the caller then receives them as the keyword `keep`).  `annot`: an LDSC
+    `.annot` / `.annot.gz` path with '@' in place of the chromosome, as in `bfile` (a runner then receives each
+    chromosome's [M, C] matrix as the keyword `annot`)."""
+    if annot is not None:
+        reject_sharded_annot()
+        if "@" not in annot:
+            raise NLDSCParameterError("a whole-genome run needs '@' in --annot (one annotation file per chromosome)")
     units = expand_bfile(bfile)
     if out is not None and "@" not in out:
         raise NLDSCParameterError("a whole-genome run needs '@' in --out (one output per chromosome)")
@@ -160,16 +168,25 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
         n_snp = m["bim"].n_snp
         rsq = RSQThreshold(1.0 / n_snp if rsq_thr is None else rsq_thr).data
         t0 = time.perf_counter()
+        annot_ = AnnotFile(annot.replace("@", m["chrom"]), m["bim"]) if annot is not None else None
+        annot_kw = {} if annot_ is None else {"annot": annot_.data}
         res, tim = runner(bed, n_snp, m["n_org"], ld_wind_.data, maf_thr_.data, std_thr_.data, rsq, m["pos"], flags,
-                          **kept_kw)
+                          **kept_kw, **annot_kw)
         ld = _Res(res)
-        df = make_output(m["bim"], ld, extra=extra) if out is None else None
-        if out is not None:
+        names = annot_.names if annot_ is not None else None
+        if out is None:
+            df = make_output(m["bim"], ld, extra=extra) if names is None else annot_output(m["bim"], ld, names,
+                                                                                          extra=extra)
+        else:
+            df = None
             path = out.replace("@", m["chrom"])
-            write_scores(path, m["bim"], ld, extra=extra)
+            write_scores(path, m["bim"], ld, extra=extra, annot_names=names)
             if write_m:
                 mm, md = m_values(m["bim"], ld)
                 write_m_file(str(Path(path).with_suffix(".M")), mm, md)
+                if names is not None:
+                    write_m_annot_file(str(Path(path).with_suffix(".M_annot")),
+                                       m_annot_values(m["bim"], ld, annot_.data, names))
         results[m["chrom"]] = df
         log.info(f"[rank {rank}] chr{m['chrom']}: M={n_snp} N={m['n_org']} "
                  f"in {time.perf_counter() - t0:.2f} s")

@@ -17,9 +17,12 @@ import pandas as pd
 from ..core.common import elapsed_time
 from ..core.logger import log
 from . import _ldscore as lds
-from .common import BIMFile, LDWindow, MAF, PLINKFile, ResidualsSTDThreshold, RSQThreshold, kept_individuals
+from ..core.common import NLDSCParameterError
+from .common import (AnnotFile, BIMFile, LDWindow, MAF, PLINKFile, ResidualsSTDThreshold, RSQThreshold,
+                     kept_individuals)
 
-__all__ = ["estimate_lds", "make_output", "format_scores", "write_scores", "show_summary", "m_values", "write_m_file"]
+__all__ = ["estimate_lds", "make_output", "format_scores", "write_scores", "show_summary", "m_values", "write_m_file",
+           "annot_output", "m_annot_values", "write_m_annot_file", "reject_sharded_annot"]
 
 
 def show_summary(ld) -> None:
@@ -87,9 +90,50 @@ def format_scores(bim: BIMFile, ld, *, extra: bool = False) -> bytes:
     return head.encode() + b"".join(parts)
 
 
-def write_scores(path: str, bim: BIMFile, ld, *, extra: bool = False) -> None:
+def write_scores(path: str, bim: BIMFile, ld, *, extra: bool = False, annot_names=None) -> None:
+    if annot_names is not None:  # partitioned scores: the same table with the per-annotation columns appended
+        annot_output(bim, ld, annot_names, extra=extra).to_csv(path, sep="\t", index=False, float_format="%.5f")
+        return
     with open(path, "wb") as fh:
         fh.write(format_scores(bim, ld, extra=extra))
+
+
+def _annot_matrix(values, n_snp: int, n_annot: int) -> np.ndarray:
+    """ld.l2_annot / ld.l2d_annot (an [M, C] array, or the pybind result's row-major list) as an [M, C] array."""
+    return np.asarray(values, dtype=np.float64).reshape(n_snp, n_annot)
+
+
+def annot_output(bim: BIMFile, ld, names, *, extra: bool = False) -> pd.DataFrame:
+    """make_output's table, every column in place, then L2_<name> for every annotation and L2D_<name> for every
+    annotation (ld.l2_annot, ld.l2d_annot)."""
+    df = make_output(bim, ld, extra=extra)
+    n, c = len(df), len(names)
+    for prefix, values in (("L2_", ld.l2_annot), ("L2D_", ld.l2d_annot)):
+        mat = _annot_matrix(values, n, c)
+        for k, name in enumerate(names):
+            df[prefix + name] = mat[:, k]
+    return df
+
+
+def m_annot_values(bim: BIMFile, ld, annot, names) -> pd.DataFrame:
+    """Per annotation, over the rows m_values keeps: M_c = sum_j a[j, c] and MD_c = sum_j a[j, c] WSDE_j / WSA_j (for
+    an all-ones column the M and MD of m_values before its integer cast).  Columns ANNOT, M, MD."""
+    df = make_output(bim, ld, extra=True).sort_values(by=["CHR", "BP"]).dropna().drop_duplicates(subset="SNP")
+    a = np.asarray(annot, dtype=np.float64).reshape(len(ld.l2), len(names))[df.index.to_numpy()]
+    ratio = (df["WSDE"] / df["WSA"]).to_numpy(dtype=np.float64)
+    return pd.DataFrame({"ANNOT": list(names), "M": a.sum(axis=0), "MD": (a * ratio[:, None]).sum(axis=0)})
+
+
+def write_m_annot_file(path: str, table: pd.DataFrame) -> None:
+    table.to_csv(path, sep="\t", index=False, float_format="%.5f")
+
+
+def reject_sharded_annot() -> None:
+    """--annot under torchrun with more than one rank: the sharded gather of the per-annotation columns is not
+    built."""
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NLDSCParameterError("--annot (partitioned LD scores) runs on one GPU: launch it without torchrun, or "
+                                  "with one rank (the ranks' tables are gathered without the per-annotation columns)")
 
 
 def m_values(bim: BIMFile, ld) -> tuple[int, int]:
@@ -172,10 +216,16 @@ def _calculate_sharded(dist, params):
 def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 1e-5, std_thr: float = 1e-5,
                  rsq_thr: float | None = None, *, out: str | None = None, extra: bool = False, summary: bool = False,
                  verbose: int = 0, write_m: bool = False, flags: int = 0, device: int | None = None,
-                 progress: bool | None = None, keep: str | None = None, remove: str | None = None):
+                 progress: bool | None = None, keep: str | None = None, remove: str | None = None,
+                 annot: str | None = None):
     """`keep` / `remove`: paths of `FID IID` lists (PLINK's / LDSC's --keep, --remove): the scores are computed on the
-    .fam lines of the first minus those of the second, in PLINK's sample order (common.kept_individuals)."""
+    .fam lines of the first minus those of the second, in PLINK's sample order (common.kept_individuals).
+    `annot`: path of an LDSC `.annot` / `.annot.gz` file (common.AnnotFile): partitioned LD scores, the table gains
+    L2_<name> and L2D_<name> columns and `write_m` also writes `<out>.M_annot`."""
+    if annot is not None:
+        reject_sharded_annot()
     bed_, bim_, fam_ = PLINKFile.parse(bfile)
+    annot_ = AnnotFile(annot, bim_) if annot is not None else None
     ld_wind_ = LDWindow(ld_wind, metric=wind_metric)
     maf_thr_ = MAF(maf_thr)
     std_thr_ = ResidualsSTDThreshold(std_thr)
@@ -197,6 +247,9 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
         params.keep = kept.tolist()
     if device is not None:
         params.device = int(device)
+    if annot_ is not None:
+        params.annot = annot_.data.ravel().tolist()
+        log.info(f"Annotations: {len(annot_.names)} columns of {annot}")
     log.info("Running the estimator. It may take a long time.")
     from ..core.progress import Progress
     bar = Progress(bim_.n_snp, "SNPs", enabled=progress)
@@ -216,10 +269,15 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
         show_summary(ld)
     if out:
         log.info("Writing data to disk...")
-        write_scores(out, bim_, ld, extra=extra)
+        write_scores(out, bim_, ld, extra=extra, annot_names=annot_.names if annot_ is not None else None)
         if write_m:
             m, md = m_values(bim_, ld)
             write_m_file(str(Path(out).with_suffix(".M")), m, md)
+            if annot_ is not None:
+                write_m_annot_file(str(Path(out).with_suffix(".M_annot")),
+                                   m_annot_values(bim_, ld, annot_.data, annot_.names))
         log.info(f"Completed. File: {out}")
         return None
+    if annot_ is not None:
+        return annot_output(bim_, ld, annot_.names, extra=extra)
     return make_output(bim_, ld, extra=extra)
