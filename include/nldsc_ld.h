@@ -36,6 +36,7 @@ extern "C" {
 #define NLDSC_E_HIP (-5)       /* HIP runtime error */
 #define NLDSC_E_OOM (-6)       /* device or host allocation failed */
 #define NLDSC_E_NODEV (-7)     /* no HIP device visible: there is no CPU fallback */
+#define NLDSC_E_SPACE (-8)     /* a caller's output array is too small; the message names the needed count */
 
 /* flags */
 #define NLDSC_FLAG_STRICT_PLINK_ORDER 1u /* use PLINK sample order in the last .bed byte (reference
@@ -114,6 +115,8 @@ void nldsc_engine_destroy(nldsc_engine* e);
  *   q_rounds     [1] quad super-items in launches of one workgroup per CU; 0 one launch
  *   defer_rep    [1] K loops of items holding a replayed rare variant in the main launch; 0 a later KC launch
  *   annot_batch_items [0] annotated runs: block-pair items per batch (0: what the Gram scratch cap holds)
+ *   pairs_batch_items [0] pairs runs: the same
+ *   pairs_max_cells   [0] pairs runs: cells of the dense count matrix a run may use (0: 2^27)
  *   debug_timing [0] per-run stage timings on stderr */
 int nldsc_engine_set_option(nldsc_engine* e, const char* name, int64_t value, char* err, size_t errlen);
 
@@ -186,6 +189,38 @@ int nldsc_engine_run(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begi
 int nldsc_engine_run_annot(nldsc_engine* e, const nldsc_ld_params* p, const double* annot, int32_t n_annot,
                            int32_t own_begin, int32_t own_end, nldsc_ld_result* r, double* l2_annot,
                            double* l2d_annot, char* err, size_t errlen);
+
+/* The pairwise LD table behind the LD scores: nldsc_engine_run plus, for every owned computed SNP j, one entry per
+ * neighbour k the run counts in l2_ws[j] — the ordered pairs (j, k) the pair epilogue adds to L2[j] — in CSR over the
+ * owned range: row_ptr[own_end - own_begin + 1] (row j - own_begin is [row_ptr[..], row_ptr[.. + 1])), then k[] (the
+ * neighbour's SNP index, ascending within a row), rv[] (the additive correlation r: the epilogue's fp64 dot product
+ * times its hoisted 1 / n_org, so r2adj(r) = 1 - (1 - r r) (n_org - 1) / (n_org - 2) is the term of L2[j]) and rdv[]
+ * (corr(A_j, R_k) likewise, the term of L2D[j]; NaN where k has no passing residual — the pair is not in l2d_ws[j] —
+ * and with NLDSC_FLAG_ADDITIVE_ONLY).  SNPs that are not computed have empty rows.  `r` is filled exactly as
+ * nldsc_engine_run fills it, bit for bit.
+ *   - Signs are those of the file's allele coding (A counts A2 copies as the .bed stores them), whatever orientation
+ *     the engine keeps a row in.
+ *   - r(j, k) and r(k, j) are the same bits.  Inside one 32-SNP block the fp64 form is symmetric only to rounding:
+ *     there the pair's entries both carry the value of the entry with j < k, so for j > k in one block r2adj(r) may
+ *     differ from the term the run added to L2[j] in the last bits.
+ *   - The table is bit-reproducible and does not depend on the schedule (engine options, batches, K-split): no
+ *     position is decided by an atomic.  Non-finite values (windows poisoned by an all-missing SNP) are emitted as
+ *     they are.
+ *   - min_r2 (NaN: no filter) keeps an entry when r2adj(r) > min_r2 or r2adj(rd) > min_r2 (strict; non-finite values
+ *     compare false and drop out).
+ *   - Sizing: row_ptr and *n_pairs are always written.  When *n_pairs > cap, or k is NULL, nothing is emitted and the
+ *     call returns NLDSC_E_SPACE with the needed count in `err`; `r` is written in that case too.  (An empty table
+ *     is NLDSC_OK whatever the capacity.)
+ *   - NLDSC_E_ARG, with the reason in `err`, unless the run takes the exact fp4 path and n_org < 2^19 (as an annotated
+ *     run), and when own_n * Wb — Wb the widest window of the owned SNPs in 32-SNP blocks — exceeds 2^27 cells
+ *     (option pairs_max_cells): narrow the owned range.  Host results only; annotations and pairs in one run are not
+ *     supported.
+ *   - The band goes in batches like an annotated run's (option pairs_batch_items): a count pass, a scan, and — when
+ *     the table is emitted — an emit pass, which computes the Gram tiles again unless one batch held the whole band.
+ *     Device memory: 4 bytes per cell and 20 bytes per pair.  Stateless: the next run is a plain one. */
+int nldsc_engine_run_pairs(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,
+                           nldsc_ld_result* r, double min_r2, int64_t* row_ptr, int32_t* k, double* rv,
+                           double* rdv, int64_t cap, int64_t* n_pairs, char* err, size_t errlen);
 
 /* nldsc_engine_run with the owned slice of the result left in device memory (the multi-GPU gather of
  * SURVEY.md §8 e1 then runs device to device over RCCL, without a host round trip): `table_dev`, device memory
@@ -280,6 +315,17 @@ int nldsc_plan_band(const double* positions, const uint8_t* flags, int32_t n_snp
 int nldsc_annot_scale_exp(double max_abs);
 int nldsc_annot_plan_batches(int32_t n_items, int32_t n_it, int32_t n_cu, int32_t ksplit_ok, int32_t batch_items,
                              int32_t* batches, int32_t cap);
+
+/* Host-only arithmetic of pairs runs (no GPU needed; the engine and its kernels use the same code).  _cell: the cell
+ * of the dense count matrix that holds owned SNP g's entries against 32-SNP block nb, (g - own_begin) * wb +
+ * (nb - L_g / 32), or -1 (g outside the owned range, L_g < 0, nb outside the wb blocks from L_g's on).
+ * _window_blocks: wb of an owned range from the pointers L, R (n_snp each): max over computed SNPs of R / 32 - L / 32
+ * + 1, at least 1.  _split_ranges: owned ranges of at most `budget` pairs from the row_ptr[n + 1] of a sizing call,
+ * ends[k] = end of range k (the ranges tile [0, n); a single row above the budget is a range of its own); returns
+ * the range count; when it exceeds `cap` (or ends == NULL) nothing is written; < 0 on bad arguments. */
+int64_t nldsc_pairs_cell(int32_t g, int32_t nb, int32_t own_begin, int32_t own_end, int32_t L_g, int32_t wb);
+int nldsc_pairs_window_blocks(const int32_t* L, const int32_t* R, int32_t n_snp, int32_t own_begin, int32_t own_end);
+int nldsc_pairs_split_ranges(const int64_t* row_ptr, int32_t n, int64_t budget, int32_t* ends, int32_t cap);
 
 /* The score table as the reference writes it (make_output + DataFrame.to_csv(sep="\t", index=False,
  * float_format="%.5f"), nldsc/ldscore/routine.py:94-101), without the header line: row i = prefix line i

@@ -58,13 +58,18 @@ def main():
 @click.option("--annot", help="Partitioned LD scores: FILE is an LDSC .annot / .annot.gz (with '@' for the chromosome "
                               "in a whole-genome run); adds L2_<name> / L2D_<name> columns and, with --write-m, "
                               "<out>.M_annot", metavar="FILE", default=None)
+@click.option("--pairs-out", help="Also write the pairwise LD table behind the scores to FILE (.gz compresses; '@' for "
+                                  "the chromosome in a whole-genome run): CHR SNP_A BP_A SNP_B BP_B R R2 RD R2D, one "
+                                  "row per SNP_A and neighbour SNP_B in its window", metavar="FILE", default=None)
+@click.option("--pairs-min-r2", help="Keep only the pairs of --pairs-out whose R2 or R2D exceeds F", metavar="F",
+              type=float, default=None)
 @click.option("--additive-only", help="Skip the dominance terms (L2D = NaN)", is_flag=True, default=False)
 @click.option("--device", help="HIP device ordinal", type=int, default=None)
 @click.option("--quiet", help="No progress lines on stderr", is_flag=True, default=False)
 @click.option("--display", help="Display traceback", is_flag=True, default=False)
 @handle_exception
 def est_ld(bfile, out, ld_wind_kb, ld_wind_cm, maf_thr, std_thr, rsq_thr, extra, write_m, strict_plink_order,
-           keep, remove, annot, additive_only, device, quiet):
+           keep, remove, annot, pairs_out, pairs_min_r2, additive_only, device, quiet):
     if sum(map(bool, [ld_wind_kb, ld_wind_cm])) != 1:
         raise RuntimeError("Please, specify exactly one --ld-wind option")
     elif ld_wind_kb:
@@ -78,11 +83,13 @@ def est_ld(bfile, out, ld_wind_kb, ld_wind_cm, maf_thr, std_thr, rsq_thr, extra,
         from .ldscore.genome import estimate_lds_genome
         estimate_lds_genome(bfile, ld_wind=ld_wind, wind_metric=wind_metric, maf_thr=maf_thr, std_thr=std_thr,
                             rsq_thr=rsq_thr, out=out, extra=extra, write_m=write_m, flags=flags, device=device,
-                            progress=not quiet, keep=keep, remove=remove, annot=annot)
+                            progress=not quiet, keep=keep, remove=remove, annot=annot, pairs_out=pairs_out,
+                            pairs_min_r2=pairs_min_r2)
         return
     estimate_lds(bfile, ld_wind=ld_wind, wind_metric=wind_metric, maf_thr=maf_thr, std_thr=std_thr,
                  rsq_thr=rsq_thr, out=out, extra=extra, summary=True, write_m=write_m, flags=flags, device=device,
-                 progress=not quiet, keep=keep, remove=remove, annot=annot)
+                 progress=not quiet, keep=keep, remove=remove, annot=annot, pairs_out=pairs_out,
+                 pairs_min_r2=pairs_min_r2)
 
 
 @main.command("h2", help="(not part of this engine) heritability estimation")

@@ -16,7 +16,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libnldsc_amd.so")
 
 OK = 0
-E_BAD_MAGIC, E_IO, E_SIZE, E_ARG, E_HIP, E_OOM, E_NODEV = -1, -2, -3, -4, -5, -6, -7
+E_BAD_MAGIC, E_IO, E_SIZE, E_ARG, E_HIP, E_OOM, E_NODEV, E_SPACE = -1, -2, -3, -4, -5, -6, -7, -8
 FLAG_STRICT_PLINK_ORDER = 1
 FLAG_ADDITIVE_ONLY = 2
 FLAG_EXACT_I8 = 4
@@ -35,6 +35,7 @@ EXPORTED = (
     "nldsc_engine_run_device_finish", "nldsc_engine_set_option", "nldsc_host_alloc", "nldsc_host_free",
     "nldsc_engine_result_direct", "nldsc_engine_set_keep", "nldsc_engine_kept", "nldsc_ld_calculate_keep",
     "nldsc_engine_run_annot", "nldsc_ld_calculate_annot", "nldsc_annot_scale_exp", "nldsc_annot_plan_batches",
+    "nldsc_engine_run_pairs", "nldsc_pairs_cell", "nldsc_pairs_window_blocks", "nldsc_pairs_split_ranges",
 )
 MAX_ANNOT = 1024  # NLDSC_MAX_ANNOT
 
@@ -140,6 +141,13 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                                                    ctypes.POINTER(Result), vp, vp] + c_err
             L.nldsc_annot_scale_exp.argtypes = [ctypes.c_double]
             L.nldsc_annot_plan_batches.argtypes = [ctypes.c_int32] * 5 + [vp, ctypes.c_int32]
+        if hasattr(L, "nldsc_engine_run_pairs"):
+            L.nldsc_engine_run_pairs.argtypes = [vp, ctypes.POINTER(Params), ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.POINTER(Result), ctypes.c_double, vp, vp, vp, vp,
+                                                 ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)] + c_err
+            L.nldsc_pairs_cell.argtypes = [ctypes.c_int32] * 6
+            L.nldsc_pairs_window_blocks.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+            L.nldsc_pairs_split_ranges.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, vp, ctypes.c_int32]
         L.nldsc_synth_bed_device.argtypes = [ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float,
                                              ctypes.c_uint64] + c_err
@@ -147,6 +155,8 @@ def lib(path: str | None = None) -> ctypes.CDLL:
             if name not in ("nldsc_version", "nldsc_device_count", "nldsc_engine_destroy", "nldsc_host_alloc",
                             "nldsc_host_free") and hasattr(L, name):
                 getattr(L, name).restype = ctypes.c_int
+        if hasattr(L, "nldsc_pairs_cell"):
+            L.nldsc_pairs_cell.restype = ctypes.c_int64
         if hasattr(L, "nldsc_format_scores"):
             L.nldsc_format_scores.restype = ctypes.c_int64
             L.nldsc_format_scores.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int32] + [vp] * 7 + \
@@ -268,3 +278,37 @@ def annot_plan_batches(n_items: int, n_it: int, n_cu: int, ksplit_ok: bool = Tru
     out = np.zeros((max(k, 1), 3), np.int32)
     assert lib().nldsc_annot_plan_batches(*args, out.ctypes.data, len(out)) == k
     return out[:k]
+
+
+def pairs_cell(g: int, nb: int, own, L_g: int, wb: int) -> int:
+    """The cell of a pairs run's dense count matrix that holds owned SNP g's entries against 32-SNP block nb, or -1
+    (C ABI nldsc_pairs_cell; host only)."""
+    return int(lib().nldsc_pairs_cell(int(g), int(nb), int(own[0]), int(own[1]), int(L_g), int(wb)))
+
+
+def pairs_window_blocks(L, R, own=None) -> int:
+    """The widest window of the owned computed SNPs in 32-SNP blocks (C ABI nldsc_pairs_window_blocks; host only)."""
+    L_ = np.ascontiguousarray(L, dtype=np.int32)
+    R_ = np.ascontiguousarray(R, dtype=np.int32)
+    own = (0, len(L_)) if own is None else own
+    k = lib().nldsc_pairs_window_blocks(L_.ctypes.data, R_.ctypes.data, len(L_), int(own[0]), int(own[1]))
+    if k < 0:
+        raise ValueError(f"nldsc_pairs_window_blocks error {k}")
+    return int(k)
+
+
+def pairs_split_ranges(row_ptr, budget: int) -> list:
+    """Owned ranges [(lo, hi), ...] of at most `budget` pairs from the row_ptr of a sizing call (C ABI
+    nldsc_pairs_split_ranges; host only): they tile [0, len(row_ptr) - 1); a single row above the budget is a range
+    of its own."""
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    n = len(rp) - 1
+    if n < 0:
+        raise ValueError("row_ptr must have at least one element")
+    k = lib().nldsc_pairs_split_ranges(rp.ctypes.data, n, int(budget), None, 0)
+    if k < 0:
+        raise ValueError(f"nldsc_pairs_split_ranges error {k}")
+    ends = np.zeros(max(k, 1), np.int32)
+    assert lib().nldsc_pairs_split_ranges(rp.ctypes.data, n, int(budget), ends.ctypes.data, len(ends)) == k
+    los = [0] + [int(x) for x in ends[:k - 1]] if k else []
+    return [(lo, int(hi)) for lo, hi in zip(los, ends[:k])]

@@ -250,6 +250,26 @@ std::vector<AnnotBatch> plan_annot_batches(int n_items, int n_it, int n_cu, bool
     return out;
 }
 
+int pairs_window_blocks(const int* L, const int* R, int own_lo, int own_hi) {
+    int wb = 1;
+    for (int g = own_lo; g < own_hi; ++g)
+        if (L[g] >= 0) wb = std::max(wb, R[g] / 32 - L[g] / 32 + 1);
+    return wb;
+}
+
+std::vector<int32_t> pairs_split_ranges(const int64_t* row_ptr, int32_t n, int64_t budget) {
+    std::vector<int32_t> ends;
+    int32_t lo = 0;
+    while (lo < n) {
+        // the last hi with row_ptr[hi] - row_ptr[lo] <= budget (row_ptr is non-decreasing), at least one row
+        const int64_t* it = std::upper_bound(row_ptr + lo, row_ptr + n + 1, row_ptr[lo] + std::max<int64_t>(budget, 0));
+        const int32_t hi = std::max<int32_t>((int32_t)(it - row_ptr) - 1, lo + 1);
+        ends.push_back(hi);
+        lo = hi;
+    }
+    return ends;
+}
+
 int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it) {
     if (use_t2) return t2_mode == 3 ? NLDSC_BAND_F4_QUAD : t2_mode == 1 ? NLDSC_BAND_F4_ROUTED : NLDSC_BAND_F4_2X2;
     if (path != 2) return path != 0 ? NLDSC_BAND_I8 : NLDSC_BAND_F32;
@@ -287,6 +307,25 @@ int nldsc_annot_plan_batches(int32_t n_items, int32_t n_it, int32_t n_cu, int32_
         batches[3 * k] = b[k].first; batches[3 * k + 1] = b[k].n; batches[3 * k + 2] = b[k].ksplit;
     }
     return (int)b.size();
+}
+
+int64_t nldsc_pairs_cell(int32_t g, int32_t nb, int32_t own_begin, int32_t own_end, int32_t L_g, int32_t wb) {
+    return nldsc::pairs_cell(g, nb, own_begin, own_end, L_g, wb);
+}
+
+int nldsc_pairs_window_blocks(const int32_t* L, const int32_t* R, int32_t n_snp, int32_t own_begin, int32_t own_end) {
+    if (!L || !R || own_begin < 0 || own_end > n_snp || own_begin > own_end) return NLDSC_E_ARG;
+    return nldsc::pairs_window_blocks(L, R, own_begin, own_end);
+}
+
+int nldsc_pairs_split_ranges(const int64_t* row_ptr, int32_t n, int64_t budget, int32_t* ends, int32_t cap) {
+    if (!row_ptr || n < 0 || budget < 0) return NLDSC_E_ARG;
+    for (int32_t j = 0; j < n; ++j)
+        if (row_ptr[j + 1] < row_ptr[j]) return NLDSC_E_ARG;
+    const std::vector<int32_t> e = nldsc::pairs_split_ranges(row_ptr, n, budget);
+    if ((int64_t)e.size() > (int64_t)cap || !ends) return (int)e.size();
+    std::copy(e.begin(), e.end(), ends);
+    return (int)e.size();
 }
 
 }  // extern "C"

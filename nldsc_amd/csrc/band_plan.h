@@ -61,6 +61,33 @@ struct AnnotBatch { int first, n, ksplit; };
 std::vector<AnnotBatch> plan_annot_batches(int n_items, int n_it, int n_cu, bool ksplit_ok, int want,
                                            size_t cap_bytes);
 
+// ---- pair tables (nldsc_engine_run_pairs): the dense count matrix and the owned ranges of a pair budget ----
+#ifdef __HIPCC__
+#define NLDSC_HD __host__ __device__
+#else
+#define NLDSC_HD
+#endif
+// The count pass stores the kept entries of owned SNP g against the 32-SNP block nb in cell
+// (g - own_lo) * Wb + (nb - L_g / 32): a row's cells in neighbour order, so the exclusive scan of the matrix is the
+// CSR layout sorted by k.  L_g: g's left pointer; Wb: pairs_window_blocks.  -1: no cell (g not owned or not computed,
+// or nb outside the Wb blocks from g's left pointer on — such a block holds no neighbour of g).
+NLDSC_HD inline int64_t pairs_cell(int g, int nb, int own_lo, int own_hi, int L_g, int Wb) {
+    if (g < own_lo || g >= own_hi || L_g < 0) return -1;
+    const int c = nb - L_g / 32;
+    if (c < 0 || c >= Wb) return -1;
+    return (int64_t)(g - own_lo) * Wb + c;
+}
+// Wb: the widest window of the owned computed SNPs in 32-SNP blocks, max (R_g / 32 - L_g / 32 + 1); at least 1
+int pairs_window_blocks(const int* L, const int* R, int own_lo, int own_hi);
+// Gram scratch of a pairs band (8 GiB: the C3 band, 26 034 items, in one batch — the emit pass then reads the count
+// pass's tiles instead of computing them again)
+constexpr size_t PAIRS_GRAM_CAP_BYTES = (size_t)8 << 30;
+// cells of the dense count matrix a run may use (option "pairs_max_cells" overrides it): 2^27 ints, 512 MiB
+constexpr int64_t PAIRS_MAX_CELLS = (int64_t)1 << 27;
+// Owned ranges of at most `budget` pairs from the row_ptr[n + 1] of a sizing call: ends[k] is the end of range k
+// (ranges tile [0, n); a single row above the budget is a range of its own; n = 0 gives none)
+std::vector<int32_t> pairs_split_ranges(const int64_t* row_ptr, int32_t n, int64_t budget);
+
 // NLDSC_BAND_* (nldsc_ld.h) of a run; path: 0 fp32, 1 int8, 2 fp4; t2_mode: option "t2"
 int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it);
 

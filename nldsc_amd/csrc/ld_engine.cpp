@@ -315,6 +315,15 @@ struct nldsc_engine {
     // option "annot_batch_items" (0: what nldsc::ANNOT_GRAM_CAP_BYTES of Gram scratch holds)
     DevBuf<double> annot_dev, annot_scale, l2c_acc, l2dc_acc, annot_out;
     int annot_batch_items = 0;
+    // pairs runs (nldsc_engine_run_pairs): the dense count matrix [own_n][Wb] (+ one int: Wb as the device found it),
+    // the row lengths, the table's row_ptr and its k / r | rd on their way to the host; options "pairs_batch_items"
+    // (as annot_batch_items) and "pairs_max_cells" (0: nldsc::PAIRS_MAX_CELLS)
+    DevBuf<int> pairs_cnt, pairs_len, pairs_k;
+    DevBuf<long long> pairs_ptr;
+    DevBuf<double> pairs_val;
+    std::vector<int> h_pairs_len;
+    int pairs_batch_items = 0;
+    int64_t pairs_max_cells = 0;
     // the device table of a run (finish_table's input), kept for a split run between its two calls
     // (nldsc_engine_run_device_split / _finish: `pending`)
     struct SplitState {
@@ -596,6 +605,8 @@ int nldsc_engine_set_option(nldsc_engine* e, const char* name, int64_t value, ch
         {"q_rounds", 0, 1, [&](int64_t v) { e->q_rounds = v != 0; }},
         {"defer_rep", 0, 1, [&](int64_t v) { e->defer_rep = v != 0; }},
         {"annot_batch_items", 0, INT32_MAX, [&](int64_t v) { e->annot_batch_items = (int)v; }},
+        {"pairs_batch_items", 0, INT32_MAX, [&](int64_t v) { e->pairs_batch_items = (int)v; }},
+        {"pairs_max_cells", 0, INT64_MAX, [&](int64_t v) { e->pairs_max_cells = v; }},
         {"debug_timing", 0, 1, [&](int64_t v) { e->debug_timing = v != 0; }},
     };
     for (const Opt& o : opts)
@@ -1419,12 +1430,126 @@ int enqueue_band_annot(nldsc_engine* e, const nldsc_ld_params* p, const RunShape
     return NLDSC_OK;
 }
 
+// A pairs run's request (nldsc_engine_run_pairs): the filter, the caller's CSR arrays and their capacity; `emitted`:
+// the table is in the device buffers, to be copied out once the stream is drained
+struct PairsRun {
+    double min_r2;
+    int64_t* row_ptr;
+    int32_t* k;
+    double *r, *rd;
+    int64_t cap;
+    int64_t* n_pairs;
+    bool emitted;
+};
+
+// The restrictions of a pairs run, each with its reason (those of an annotated run: the same two kernels' inputs).
+int prepare_pairs(const nldsc_ld_params* p, const RunShape& s, const PairsRun& pr, bool annot, char* err,
+                  size_t errlen) {
+    if (!pr.row_ptr || !pr.n_pairs) return set_err(err, errlen, NLDSC_E_ARG, "row_ptr or n_pairs is NULL");
+    if (pr.cap < 0) return set_err(err, errlen, NLDSC_E_ARG, "negative capacity %lld", (long long)pr.cap);
+    if (pr.k && pr.cap > 0 && (!pr.r || !pr.rd)) return set_err(err, errlen, NLDSC_E_ARG, "r or rd is NULL beside k");
+    if (annot) return set_err(err, errlen, NLDSC_E_ARG, "annotations and a pair table in one run are not supported");
+    if (p->n_org >= (1 << 19))
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "pairs runs need n_org < 2^19 (got %d): the K-split partial kernel takes unsegmented rows",
+                       p->n_org);
+    if (s.path != 2)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "pairs runs take the exact fp4 path only: this run's flags or the band_mode option select %s",
+                       s.path == 0 ? "fp32" : "exact int8");
+    return NLDSC_OK;
+}
+
+// The band of a pairs run (ev[3] .. ev[4]): after the rare-variant replay, the single-block items in batches (as an
+// annotated band's) through the K-split partial kernel and the count pass of the pairs epilogue, which also adds the
+// ordinary sums; the row scan, the row lengths to the host, row_ptr and the pair count there; then, when the caller's
+// arrays hold the table, the emit pass over the same batches — their Gram tiles computed again unless one batch held
+// the whole band.  The host waits for the stream twice (the window width, the row lengths).
+int enqueue_band_pairs(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m,
+                       const Schedule& sc, PairsRun& pr, char* err, size_t errlen) {
+    hipStream_t st = e->stream, cs = e->copy_stream;
+    const int n_items = sc.n_items, n_own = s.own_end - s.own_begin;
+    HIPCHK(hipEventRecord(e->ev[3], st));
+    const std::vector<nldsc::AnnotBatch> batches = nldsc::plan_annot_batches(
+        n_items, s.n_it, e->n_cu, e->ksplit_ok, e->pairs_batch_items, nldsc::PAIRS_GRAM_CAP_BYTES);
+    size_t units = 0;
+    int p_max = 1;
+    for (const nldsc::AnnotBatch& b : batches) {
+        units = std::max(units, (size_t)b.n * (size_t)b.ksplit);
+        p_max = std::max(p_max, b.ksplit);
+    }
+    e->n_band_items = n_items;
+    e->last_ksplit = p_max;
+    e->last_round_items = 0;
+    e->last_tail_ksplit = 1;
+    e->last_band_kernel = NLDSC_BAND_F4_KSPLIT;
+    HIPCHK(e->gram.ensure(std::max<size_t>(units, 1) * 8192));
+    const nldsc::BandArgs a = fill_band_args(e, p, s, m);
+    // the widest window of the owned range in blocks, from the device's pointers
+    HIPCHK(e->pairs_len.ensure((size_t)n_own + 1));
+    int Wb = 1;
+    HIPCHK(nldsc::launch_pairs_window_blocks(e->Lw.p, e->Rw.p, s.own_begin, s.own_end, e->pairs_len.p + n_own, st));
+    HIPCHK(hipMemcpyAsync(&Wb, e->pairs_len.p + n_own, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int64_t max_cells = e->pairs_max_cells > 0 ? e->pairs_max_cells : nldsc::PAIRS_MAX_CELLS;
+    if (Wb < 1 || (int64_t)n_own * Wb > max_cells)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "the count matrix of %d owned SNPs x %d window blocks exceeds %lld cells: narrow the owned range "
+                       "to at most %lld SNPs", n_own, Wb, (long long)max_cells, (long long)(max_cells / std::max(Wb, 1)));
+    const size_t cells = (size_t)n_own * (size_t)Wb;
+    HIPCHK(e->pairs_cnt.ensure(cells));
+    HIPCHK(hipMemsetAsync(e->pairs_cnt.p, 0, sizeof(int) * cells, st));
+    nldsc::PairsArgs pa = {e->pairs_cnt.p, Wb, nullptr, 0, nullptr, nullptr, nullptr, pr.min_r2,
+                           e->oriented ? e->flip.p : nullptr, e->counts.p};
+    // the epilogue reads the replayed constants of the KC items: the whole band waits for the replay
+    if (s.replay) HIPCHK(hipStreamWaitEvent(st, e->ev_replay, 0));
+    for (const nldsc::AnnotBatch& b : batches)
+        HIPCHK(nldsc::launch_band_f4_pairs(a, pa, b.ksplit, e->items.p + b.first, b.n, e->gram.p, false, true));
+    HIPCHK(nldsc::launch_pairs_row_scan(e->pairs_cnt.p, Wb, n_own, e->pairs_len.p, st));
+    e->h_pairs_len.resize((size_t)n_own);
+    HIPCHK(hipMemcpyAsync(e->h_pairs_len.data(), e->pairs_len.p, sizeof(int) * (size_t)n_own, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int64_t total = 0;
+    for (int j = 0; j < n_own; ++j) {
+        pr.row_ptr[j] = total;
+        total += e->h_pairs_len[(size_t)j];
+    }
+    pr.row_ptr[n_own] = total;
+    *pr.n_pairs = total;
+    if (pr.k && total <= pr.cap && total > 0) {
+        const size_t T = (size_t)total;
+        HIPCHK(e->pairs_ptr.ensure((size_t)n_own + 1));
+        HIPCHK(e->pairs_k.ensure(T));
+        HIPCHK(e->pairs_val.ensure(2 * T));
+        HIPCHK(hipMemcpyAsync(e->pairs_ptr.p, pr.row_ptr, sizeof(int64_t) * ((size_t)n_own + 1), hipMemcpyHostToDevice, st));
+        pa.row_ptr = e->pairs_ptr.p, pa.n_pairs = total, pa.k = e->pairs_k.p, pa.r = e->pairs_val.p;
+        pa.rd = e->pairs_val.p + T;
+        for (const nldsc::AnnotBatch& b : batches)
+            HIPCHK(nldsc::launch_band_f4_pairs(a, pa, b.ksplit, e->items.p + b.first, b.n, e->gram.p, true,
+                                               batches.size() > 1));
+        pr.emitted = true;
+    }
+    e->last_path = s.path;
+    HIPCHK(hipEventRecord(e->ev[4], st));
+    HIPCHK(e->sums.ensure(3));
+    HIPCHK(e->h_sums.ensure(3 * sizeof(unsigned long long)));
+    HIPCHK(hipStreamWaitEvent(cs, e->ev[3], 0));
+    HIPCHK(hipMemsetAsync(e->sums.p + 2, 0, sizeof(unsigned long long), cs));
+    HIPCHK(nldsc::launch_issued_products(e->items.p, n_items, nullptr, 0, m.gpu_plan ? e->plan_rows.p : nullptr,
+                                         e->blk_miss.p, s.nblk, s.path, s.dom, 0, m.route_shift, e->sums.p + 2, cs));
+    HIPCHK(hipMemcpyAsync(e->h_sums.p + 2 * sizeof(unsigned long long), e->sums.p + 2, sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipEventRecord(e->ev_issued, cs));
+    return NLDSC_OK;
+}
+
 // The band on the main stream (ev[3] .. ev[4]): the super-item launch, the wait for the compacted count, the
 // single-block launches, the KC launches after the replay (ev_replay), or the fp32 launch; then the issued-product
 // count on the side stream (ev_issued).
 int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m, const Schedule& sc,
-                 char* err, size_t errlen, const AnnotRun* an = nullptr) {
+                 char* err, size_t errlen, const AnnotRun* an = nullptr, PairsRun* pr = nullptr) {
     if (an) return enqueue_band_annot(e, p, s, m, sc, *an, err, errlen);
+    if (pr) return enqueue_band_pairs(e, p, s, m, sc, *pr, err, errlen);
     hipStream_t st = e->stream, cs = e->copy_stream;
     const int n_items = sc.n_items;
     HIPCHK(hipEventRecord(e->ev[3], st));
@@ -1584,18 +1709,22 @@ int finish_host(nldsc_engine* e, const RunShape& s, const HostOut& o, double* sw
 // stops before finalize; nldsc_engine_run_device_finish adds the left neighbour's export and finishes.
 int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end, nldsc_ld_result* r,
              double* table_dev, int32_t width, char* err, size_t errlen, long long* export_dev = nullptr,
-             int32_t export_cap = 0, int32_t* export_n = nullptr, const AnnotRun* an = nullptr) {
+             int32_t export_cap = 0, int32_t* export_n = nullptr, const AnnotRun* an = nullptr,
+             PairsRun* pr = nullptr) {
     const bool split = export_n != nullptr;
     int rc = check_run_args(e, p, own_begin, own_end, r, table_dev, width, split, export_dev, export_cap, err, errlen);
     if (rc) return rc;
     if (an && (rc = prepare_annot(e, p, run_shape(e, p, own_begin, own_end, split), *an, err, errlen))) return rc;
+    if (pr && (rc = prepare_pairs(p, run_shape(e, p, own_begin, own_end, split), *pr, an != nullptr, err, errlen)))
+        return rc;
+    if (pr && own_begin == own_end) pr->row_ptr[0] = *pr->n_pairs = 0;
     if (own_begin == own_end) return run_nothing_owned(e, p->n_snp, own_begin, table_dev, width, err, errlen);
     HIPCHK(hipSetDevice(e->device));
     HostOut out = {};
     e->last_direct = -1;
     if (!table_dev && (rc = resolve_host_out(e, r, own_begin, own_end, &out, err, errlen))) return rc;
     const RunShape s = run_shape(e, p, own_begin, own_end, split);
-    const PlanMode m = plan_mode(e, p, s, an != nullptr);
+    const PlanMode m = plan_mode(e, p, s, an != nullptr || pr != nullptr);
     if ((rc = ensure_run_buffers(e, s, m, err, errlen))) return rc;
 
     const auto t_start = Clock::now();
@@ -1607,7 +1736,7 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     if (rc) return rc;
     // (l2_acc, l2d_acc and ws_acc were zeroed by snp_stats_kernel)
     const auto t_host1 = Clock::now();
-    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen, an))) return rc;
+    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen, an, pr))) return rc;
     if (an) {  // the per-annotation scores of the owned slice, finalized beside the ordinary ones (.. ev[5])
         double* o2 = e->annot_out.p;
         HIPCHK(nldsc::launch_finalize_annot(e->Lw.p, e->ws_acc.p, annot_args(e, s, *an), s.M, own_begin, own_end, s.dom,
@@ -1636,6 +1765,12 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
         if (an->l2d)
             HIPCHK(hipMemcpy2D(an->l2d + own_begin, sizeof(double) * (size_t)s.M, e->annot_out.p + (size_t)an->n * n_own,
                                row, row, (size_t)an->n, hipMemcpyDeviceToHost));
+    }
+    if (pr && pr->emitted) {  // (the stream is drained) the table into the caller's arrays
+        const size_t T = (size_t)*pr->n_pairs;
+        HIPCHK(hipMemcpy(pr->k, e->pairs_k.p, sizeof(int32_t) * T, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pr->r, e->pairs_val.p, sizeof(double) * T, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pr->rd, e->pairs_val.p + T, sizeof(double) * T, hipMemcpyDeviceToHost));
     }
     {
         const auto t0 = Clock::now();
@@ -1677,6 +1812,19 @@ int nldsc_engine_run_annot(nldsc_engine* e, const nldsc_ld_params* p, const doub
     if (!r) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
     const AnnotRun an = {annot, n_annot, l2_annot, l2d_annot};
     return run_impl(e, p, own_begin, own_end, r, nullptr, 0, err, errlen, nullptr, 0, nullptr, &an);
+}
+
+int nldsc_engine_run_pairs(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,
+                           nldsc_ld_result* r, double min_r2, int64_t* row_ptr, int32_t* k, double* rv, double* rdv,
+                           int64_t cap, int64_t* n_pairs, char* err, size_t errlen) {
+    if (!r) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
+    PairsRun pr = {min_r2, row_ptr, k, rv, rdv, cap, n_pairs, false};
+    const int rc = run_impl(e, p, own_begin, own_end, r, nullptr, 0, err, errlen, nullptr, 0, nullptr, nullptr, &pr);
+    if (rc) return rc;
+    if (*n_pairs > 0 && !pr.emitted)
+        return set_err(err, errlen, NLDSC_E_SPACE, "the pair table needs room for %lld pairs (capacity %lld)",
+                       (long long)*n_pairs, (long long)(k ? cap : 0));
+    return NLDSC_OK;
 }
 
 int nldsc_engine_run_device(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,

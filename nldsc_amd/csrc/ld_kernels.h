@@ -173,6 +173,30 @@ hipError_t launch_band_f4_annot(const BandArgs& a, const AnnotArgs& an, int P, c
 // device memory; out_l2d may be nullptr), NaN where the plain L2 / L2D are (and L2D everywhere without dom)
 hipError_t launch_finalize_annot(const int* Lw, const int* ws_acc, const AnnotArgs& an, int n_snp, int own_lo,
                                  int own_hi, bool dom, double* out_l2, double* out_l2d, hipStream_t st);
+// Pair tables (nldsc_engine_run_pairs): the dense count matrix cnt[own_n][Wb] (band_plan.h pairs_cell; zeroed before
+// the count pass, turned into each row's exclusive offsets by launch_pairs_row_scan), and for the emit pass the
+// table's row_ptr (own_n + 1, device memory), its n_pairs entries k / r / rd; min_r2: NaN = no filter; flip (or
+// nullptr) and counts: the stored orientation and the genotype counts (launch_snp_stats), for the signs of r and rd
+struct PairsArgs {
+    int* cnt;
+    int Wb;
+    const long long* row_ptr;
+    long long n_pairs;
+    int* k;
+    double *r, *rd;
+    double min_r2;
+    const uint8_t* flip;
+    const int* counts;
+};
+// one batch of a pairs band: band_f4_part_kernel into `gram` as launch_band_f4_annot runs it (run_part; false: the
+// batch's tiles are still there), then band_f4_epi_pairs_kernel and, with a.blk_rep, its KC instantiation — the
+// count pass (emit false: the ordinary per-SNP sums as band_f4_epi_kernel adds them plus the cell counts) or the
+// emit pass (no sums; every kept entry to its final position)
+hipError_t launch_band_f4_pairs(const BandArgs& a, const PairsArgs& pa, int P, const int4* items, int n_items,
+                                float* gram, bool emit, bool run_part);
+// out[0] = pairs_window_blocks of the owned range, on the device's left / right pointers
+hipError_t launch_pairs_window_blocks(const int* Lw, const int* Rw, int own_lo, int own_hi, int* out, hipStream_t st);
+hipError_t launch_pairs_row_scan(int* cnt, int Wb, int n_own, int* row_len, hipStream_t st);
 // 2 x 2 block-pair workgroups (unsegmented rows, gpu plan): super-items (I2, J2, 1, 0) over row / column
 // super-blocks of two 32-SNP blocks, planned from the single-block rows (launch_plan) by launch_plan_super (meta2
 // as meta; counts2 capacity ceil(nblk2/16)^2) and launch_plan_emit_super; the kernel reads `rows` (nblk) to skip the

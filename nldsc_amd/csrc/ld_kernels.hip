@@ -3095,6 +3095,271 @@ __global__ void __launch_bounds__(256) finalize_annot_kernel(
     if (out_l2d != nullptr) out_l2d[o] = d2;
 }
 
+// ---- the pairwise LD table: the (k, r, rd) of every ordered pair (j, k) the plain run counts in WSA[j] ----
+// A pairs run sends every block pair through band_f4_part_kernel and then through band_f4_epi_pairs_kernel, the annotated
+// epilogue's pair loop (pair_epilogue<DOM, f32x16v, true, KC> expression for expression: with EMIT = false it adds
+// the ordinary sums, bitwise a plain run's) with the pairs themselves as its sink, in CSR over the owned SNPs, each
+// row sorted by k, no position decided by an atomic:
+//   count (EMIT = false): every owned slot SNP g's kept entries against the item's other block nb, stored plainly to
+//     the dense cnt[pairs_cell(g, nb)] (band_plan.h; one item produces each cell: the item of g's block and nb);
+//   scan (pairs_row_scan_kernel + the host's 64-bit prefix over the row lengths): each cell's offset in its row and
+//     row_ptr;
+//   emit (EMIT = true, no sums): the same flags again, each kept entry to row_ptr[g] + cell offset + its rank in the
+//     cell.  Ranks follow k: a row SNP's 32 neighbours of one register lie in the 32 lanes of its half-wave (a ballot);
+//     a column SNP's lie in its two lanes' 16 registers each, rows 8q .. 8q + 3 in lane (i, 0) and 8q + 4 .. 8q + 7 in
+//     lane (i, 1) (an in-lane prefix plus the partner's per-q counts, xlane<32>).
+// r = dot * (1 / N) as R2Adj forms it, rd likewise (NaN where the pair is not in WSD[j]); in a diagonal item the
+// entries below the diagonal take the transposed entry's r (the fp64 form is symmetric only to rounding), so r(j, k)
+// and r(k, j) are the same bits everywhere.  Signs are those of the file's coding: a row stored flipped (flip[j]:
+// 00 <-> 11 swapped at load) has A negated and R unchanged (snp_stats_kernel), except a replayed rare variant, whose
+// constants describe the reference's vectors of the file's coding (reference_residual_kernel; KC items only), so
+// r takes the product of both SNPs' signs and rd the sign of the SNP whose A it holds.  min_r2 (NaN: off) keeps an entry when r2adj(r) or r2adj(rd) exceeds it.
+template <bool DOM, bool KC, bool EMIT>
+__global__ void __launch_bounds__(64) band_f4_epi_pairs_kernel(
+    const SnpConst* __restrict__ cst, const int4* __restrict__ items, const double* __restrict__ pos,
+    const int* __restrict__ Lw, const int* __restrict__ Rw, const uint8_t* __restrict__ sflags, int n_snp,
+    double ld_wind, double n_org, double rsq_thr, int own_lo, int own_hi, double* __restrict__ l2_acc,
+    double* __restrict__ l2d_acc, int* __restrict__ ws_acc, const uint8_t* __restrict__ blk_rep, int P,
+    const float* __restrict__ gram, int* __restrict__ cnt, int Wb, const long long* __restrict__ row_ptr,
+    long long n_pairs, int* __restrict__ out_k, double* __restrict__ out_r, double* __restrict__ out_rd,
+    double min_r2, const uint8_t* __restrict__ flip, const int* __restrict__ counts) {
+    __shared__ AnnotSlots sh;
+    __shared__ double ssgn[64];  // per slot: -1 where the stored A is the file's negated
+    __shared__ float tr[32 * 33];
+    __shared__ double trd[32 * 33];
+    // per slot: its cell of the count matrix (count pass) or its cell's first position in the table (emit pass); -1
+    // where the slot SNP has no row (not owned, not computed, a diagonal item's column slots)
+    __shared__ long long sbase[64];
+    const int4 it = items[blockIdx.x];
+    if (skip_item<KC>(blk_rep, it)) return;
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int I = it.x, J = it.y;
+    const bool diag = I == J;
+    {
+        const int s = lane;
+        const int g = s < 32 ? I * 32 + s : J * 32 + (s & 31);
+        SnpSlot si;
+        si.g = g;
+        if (g < n_snp) {
+            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
+        } else {
+            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
+        }
+        sh.info[s] = si;
+        sh.cst[s] = cst[g];
+        long long cell = g < n_snp && !(diag && s >= 32) ? pairs_cell(g, s < 32 ? J : I, own_lo, own_hi, si.L, Wb) : -1;
+        if (EMIT && cell >= 0) cell = row_ptr[g - own_lo] + cnt[cell];
+        sbase[s] = cell;
+        ssgn[s] = g < n_snp && flip != nullptr && flip[g] && !(KC && replayed_snp(counts, flip, sflags, g)) ? -1.0 : 1.0;
+    }
+    f32x16v g8[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) g8[t] = f32x16v{};
+    const float* src = gram + (size_t)blockIdx.x * P * 8192 + lane * 16;
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const float4* q = reinterpret_cast<const float4*>(src + (size_t)p * 8192 + t * 1024);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 v = q[k];
+                g8[t][4 * k] += v.x; g8[t][4 * k + 1] += v.y; g8[t][4 * k + 2] += v.z; g8[t][4 * k + 3] += v.w;
+            }
+        }
+    __syncthreads();
+    if (diag) {  // m.x(a, b) = x.m(b, a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = g8[1][r];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) g8[2][r] = tr[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
+    }
+    // ---- the plain epilogue (pair_epilogue, MB basis), each pair's correlations kept ----
+    const SnpSlot* info = sh.info;
+    const f32x16v &gxx = g8[0], &gxo = g8[1], &gox = g8[2], &goo = g8[3], &gxh = g8[4], &goh = g8[5], &ghx = g8[6],
+                  &gho = g8[7];
+    const double kslots = n_org;
+    const R2Adj r2adj(n_org);
+    const double qnan = __builtin_nan("");
+    const int sj = 32 + i;
+    const SnpSlot cj = info[sj];
+    const double sgj = ssgn[sj];
+    // the lane's 16 pairs: r, rd of the row SNP's entry (A_i . R_j) and of the column SNP's (R_i . A_j), and which of
+    // the 16 the row SNP (bit r of m_row: nij) and the column SNP (m_col: nji) need
+    double va[16], vd_row[16], vd_col[16];
+    unsigned m_row = 0, m_col = 0;
+    {
+        const SnpConst kj = sh.cst[sj];
+        const bool rpj = (cj.fl & 2) != 0;
+        SlotSum col = {0.0, 0.0, 0}, mine = {0.0, 0.0, 0};
+        int my_row = -1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {  // row group q: registers r = 4q + k, rows k + 8q + 4h
+            SlotSum rowv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int r = 4 * q + k;
+                const int si = k + 8 * q + 4 * h;
+                const SnpSlot ci = info[si];
+                const bool rpi = (ci.fl & 2) != 0;
+                const PairNeed need = pair_need(ci, cj, diag, ld_wind);
+                const bool nij = need.nij, nji = need.nji;
+                // (a diagonal item's entry above the diagonal also serves the one below it)
+                const bool nrev = diag && si < i && pair_need(cj, ci, true, ld_wind).nij;
+                SlotSum rv = {0.0, 0.0, 0};
+                va[r] = 0.0;
+                vd_row[r] = vd_col[r] = qnan;
+                if (nij || nji || nrev) {
+                    const SnpConst ki = sh.cst[si];
+                    const double mm = (double)goo[r];
+                    const double xx = 0.25 * ((double)gxx[r] - (double)gxo[r] - (double)gox[r] + mm);
+                    const double xo = ki.X - 0.5 * ((double)gxo[r] - mm);
+                    const double ox = kj.X - 0.5 * ((double)gox[r] - mm);
+                    const double oo = ki.Ob + kj.Ob - kslots + mm;
+                    const double aa = (xx - kj.mu * xo - ki.mu * (ox - kj.mu * oo)) * (ki.isa * kj.isa) +
+                                      (KC ? kj.ka * ki.SA + ki.ka * (kj.SA + kj.ka * n_org) : 0.0);
+                    const double r2 = r2adj(aa);
+                    const double sgi = ssgn[si];
+                    va[r] = aa * r2adj.inv_n * (sgi * sgj);
+                    if (nij) { rv.l2 = r2; rv.cnt = 1; m_row |= 1u << r; }
+                    if (nji) { col.l2 += r2; col.cnt += 1; m_col |= 1u << r; }
+                    if (DOM) {
+                        if (nij && rpj) {  // A_i . R_j -> L2D_i
+                            const double xh = 0.5 * ((double)gxh[r] - (double)goh[r]);
+                            const double oh = kj.H - (double)goh[r];
+                            const double ar = (2.0 * xh - kj.beta * xx - kj.c * xo -
+                                               ki.mu * (2.0 * oh - kj.beta * ox - kj.c * oo)) * (ki.isa * kj.is) +
+                                              (KC ? kj.kr * ki.SA + ki.ka * (kj.SR + kj.kr * n_org) : 0.0);
+                            const double rd = r2adj(ar);
+                            rv.l2d = rd;
+                            rv.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
+                            vd_row[r] = ar * r2adj.inv_n * sgi;
+                        }
+                        if (!diag && nji && rpi) {  // R_i . A_j -> L2D_j
+                            const double hx = 0.5 * ((double)ghx[r] - (double)gho[r]);
+                            const double ho = ki.H - (double)gho[r];
+                            const double ra = (2.0 * hx - ki.beta * xx - ki.c * ox -
+                                               kj.mu * (2.0 * ho - ki.beta * xo - ki.c * oo)) * (ki.is * kj.isa) +
+                                              (KC ? ki.kr * kj.SA + kj.ka * (ki.SR + ki.kr * n_org) : 0.0);
+                            const double rd = r2adj(ra);
+                            col.l2d += rd;
+                            col.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
+                            vd_col[r] = ra * r2adj.inv_n * sgj;
+                        }
+                    }
+                }
+                rowv[k] = rv;
+            }
+            if (!EMIT) {
+                const SlotSum t = reduce_rows4(rowv, i);  // lanes i >> 3 == k: row k + 8q + 4h
+                if ((i & 7) == q) {
+                    mine = t;
+                    my_row = (i >> 3) + 8 * q + 4 * h;
+                }
+            }
+        }
+        if (!EMIT) {
+            col = col + xlane<32>(col);  // the partner lane (i, 1 - h) holds the other 16 rows of column i
+            if (my_row >= 0) flush_slot(info[my_row], mine, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
+            if (h == 0) flush_slot(cj, col, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
+        }
+    }
+    if (diag) {  // r(a, b) for a > b from the entry (b, a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) trd[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = va[r];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int si = (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (si > i) va[r] = trd[i * 33 + si];
+        }
+    }
+    // ---- the kept entries: r2adj of the emitted values against min_r2 (a non-finite value compares false) ----
+    const bool filt = min_r2 == min_r2;
+    auto above = [&](double c) { return 1. - (1. - c * c) * r2adj.q > min_r2; };
+    // the row SNPs' entries: register r holds row (r & 3) + 8 (r >> 2) + 4h against the 32 columns of the half-wave
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int si = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const long long base = sbase[si];
+        const bool keep = ((m_row >> r) & 1) && base >= 0 && (!filt || above(va[r]) || (DOM && above(vd_row[r])));
+        const unsigned long long b = __ballot(keep);
+        const unsigned half = (unsigned)(b >> (32 * h));
+        if (!EMIT) {
+            if (i == 0 && base >= 0) cnt[base] = __popc(half);
+        } else if (keep) {
+            const long long at = base + __popc(half & ((1u << i) - 1u));
+            if (at < n_pairs) {
+                out_k[at] = cj.g;
+                out_r[at] = va[r];
+                out_rd[at] = DOM ? vd_row[r] : qnan;
+            }
+        }
+    }
+    // the column SNPs' entries (off the diagonal): rows in the order q, h, k
+    if (!diag) {
+        const long long base = sbase[sj];
+        unsigned keep = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (((m_col >> r) & 1) && base >= 0 && (!filt || above(va[r]) || (DOM && above(vd_col[r])))) keep |= 1u << r;
+        int mine4 = 0;  // byte q: the lane's kept entries of row group q
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mine4 |= __popc((keep >> (4 * q)) & 0xFu) << (8 * q);
+        const int other4 = xlane<32>(mine4);
+        if (!EMIT) {
+            const int both = mine4 + other4;
+            if (h == 0 && base >= 0)
+                cnt[base] = (both & 0xFF) + ((both >> 8) & 0xFF) + ((both >> 16) & 0xFF) + ((both >> 24) & 0xFF);
+        } else {
+            int before = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int m = (mine4 >> (8 * q)) & 0xFF, o = (other4 >> (8 * q)) & 0xFF;
+                int rank = before + (h ? o : 0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int r = 4 * q + k;
+                    if ((keep >> r) & 1) {
+                        const long long at = base + rank++;
+                        if (at < n_pairs) {
+                            out_k[at] = info[k + 8 * q + 4 * h].g;
+                            out_r[at] = va[r];
+                            out_rd[at] = DOM ? vd_col[r] : qnan;
+                        }
+                    }
+                }
+                before += m + o;
+            }
+        }
+    }
+}
+
+// one thread per owned SNP: its row of the count matrix to exclusive offsets in place, the row's length to row_len
+__global__ void __launch_bounds__(256) pairs_row_scan_kernel(int* __restrict__ cnt, int Wb, int n_own,
+                                                             int* __restrict__ row_len) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_own) return;
+    int* c = cnt + (size_t)g * Wb;
+    int run = 0;
+    for (int b = 0; b < Wb; ++b) {
+        const int t = c[b];
+        c[b] = run;
+        run += t;
+    }
+    row_len[g] = run;
+}
+
+// out[0] = max over the owned computed SNPs of their window's 32-SNP blocks (band_plan.h pairs_window_blocks;
+// out[0] starts at 1)
+__global__ void __launch_bounds__(256) pairs_window_blocks_kernel(const int* __restrict__ Lw,
+                                                                  const int* __restrict__ Rw, int own_lo, int own_hi,
+                                                                  int* __restrict__ out) {
+    const int g = own_lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= own_hi || Lw[g] < 0) return;
+    atomicMax(out, Rw[g] / 32 - Lw[g] / 32 + 1);
+}
+
 // ------------------------------------------------------------------------------------------
 // 4. finalize
 // ------------------------------------------------------------------------------------------
@@ -3571,6 +3836,49 @@ hipError_t launch_band_f4_annot(const BandArgs& a, const AnnotArgs& an, int P, c
     if (a.dom) NLDSC_EPI(true, false); else NLDSC_EPI(false, false);
     if (a.blk_rep) { if (a.dom) NLDSC_EPI(true, true); else NLDSC_EPI(false, true); }
 #undef NLDSC_EPI
+    return hipGetLastError();
+}
+
+hipError_t launch_band_f4_pairs(const BandArgs& a, const PairsArgs& pa, int P, const int4* items, int n_items,
+                                float* gram, bool emit, bool run_part) {
+    if (n_items <= 0) return hipSuccess;
+    if (a.n_it > F4_SEG_CHUNKS || P < 1 || 2 * P > a.n_it || pa.cnt == nullptr || pa.Wb < 1) return hipErrorInvalidValue;
+    if (emit && (!pa.row_ptr || !pa.k || !pa.r || !pa.rd)) return hipErrorInvalidValue;
+    const dim3 grid_p((unsigned)n_items * (unsigned)P);
+    if (run_part) {
+        if (a.dom) hipLaunchKernelGGL((band_f4_part_kernel<true>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items,
+                                      A_SNPS, P, gram, nullptr, a.route_shift);
+        else hipLaunchKernelGGL((band_f4_part_kernel<false>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS,
+                                P, gram, nullptr, a.route_shift);
+    }
+#define NLDSC_EPI(DOM_, KC_, EMIT_)                                                                                  \
+    hipLaunchKernelGGL((band_f4_epi_pairs_kernel<DOM_, KC_, EMIT_>), dim3(n_items), dim3(64), 0, a.st, a.cst, items, \
+                       A_SNPS, A_EPI, a.blk_rep, P, gram, pa.cnt, pa.Wb, pa.row_ptr, pa.n_pairs, pa.k, pa.r, pa.rd,   \
+                       pa.min_r2, pa.flip, pa.counts)
+#define NLDSC_EPI2(KC_)                                                                                              \
+    do {                                                                                                             \
+        if (a.dom) { if (emit) NLDSC_EPI(true, KC_, true); else NLDSC_EPI(true, KC_, false); }                       \
+        else { if (emit) NLDSC_EPI(false, KC_, true); else NLDSC_EPI(false, KC_, false); }                           \
+    } while (0)
+    NLDSC_EPI2(false);
+    if (a.blk_rep) NLDSC_EPI2(true);
+#undef NLDSC_EPI2
+#undef NLDSC_EPI
+    return hipGetLastError();
+}
+
+hipError_t launch_pairs_window_blocks(const int* Lw, const int* Rw, int own_lo, int own_hi, int* out, hipStream_t st) {
+    static const int one = 1;
+    hipError_t r = hipMemcpyAsync(out, &one, sizeof(int), hipMemcpyHostToDevice, st);
+    if (r != hipSuccess || own_hi <= own_lo) return r;
+    hipLaunchKernelGGL(pairs_window_blocks_kernel, dim3((own_hi - own_lo + 255) / 256), dim3(256), 0, st, Lw, Rw,
+                       own_lo, own_hi, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_pairs_row_scan(int* cnt, int Wb, int n_own, int* row_len, hipStream_t st) {
+    if (n_own <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pairs_row_scan_kernel, dim3((n_own + 255) / 256), dim3(256), 0, st, cnt, Wb, n_own, row_len);
     return hipGetLastError();
 }
 

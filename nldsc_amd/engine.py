@@ -149,6 +149,51 @@ class Engine:
                                                ctypes.byref(res), err, len(err)), err)
         return arrs
 
+    def size_pairs(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, min_r2=None):
+        """The sizing call of `run_pairs` alone (C ABI nldsc_engine_run_pairs without arrays): the usual dict plus
+        "row_ptr" (int64, own[1] - own[0] + 1) and "n_pairs"."""
+        return self._pairs(ld_wind, maf, std_thr, rsq_thr, positions, own, flags, min_r2, emit=False)
+
+    def run_pairs(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, min_r2=None):
+        """`run` plus the pairwise LD table of the owned SNPs (C ABI nldsc_engine_run_pairs: a sizing call, then the
+        emitting call into arrays of that size).  The dict also holds the CSR table: "row_ptr" (int64, own[1] - own[0]
+        + 1; row j - own[0] is SNP j's), "k" (int32: the neighbour, ascending within a row), "r" (float64: the
+        additive correlation) and "rd" (float64: corr(A_j, R_k), NaN where the pair is not in l2d_ws[j]); with
+        `min_r2` only the entries whose r2adj(r) or r2adj(rd) exceeds it."""
+        return self._pairs(ld_wind, maf, std_thr, rsq_thr, positions, own, flags, min_r2, emit=True)
+
+    def _pairs(self, ld_wind, maf, std_thr, rsq_thr, positions, own, flags, min_r2, emit, cap=None):
+        n = self.n_snp
+        own = (0, n) if own is None else own
+        p, _keep = _lib.make_params(n, self.n_org, ld_wind, maf, std_thr, rsq_thr, positions, flags=flags)
+        arrs, res = _lib.alloc_result(n)
+        thr = float("nan") if min_r2 is None else float(min_r2)
+        row_ptr = np.zeros(max(int(own[1]) - int(own[0]), 0) + 1, np.int64)
+        n_pairs = ctypes.c_int64(0)
+
+        def call(k, r, rd, cap_):
+            err = _lib.errbuf()
+            rc = self._L.nldsc_engine_run_pairs(
+                self._h, ctypes.byref(p), int(own[0]), int(own[1]), ctypes.byref(res), thr, row_ptr.ctypes.data,
+                None if k is None else k.ctypes.data, None if r is None else r.ctypes.data,
+                None if rd is None else rd.ctypes.data, int(cap_), ctypes.byref(n_pairs), err, len(err))
+            return rc, err
+
+        if cap is None:
+            rc, err = call(None, None, None, 0)
+            if rc not in (_lib.OK, _lib.E_SPACE):
+                _lib.check(rc, err)
+            cap = int(n_pairs.value)
+        arrs.update(row_ptr=row_ptr, n_pairs=int(n_pairs.value))
+        if not emit:
+            return arrs
+        k, r, rd = np.empty(cap, np.int32), np.empty(cap, np.float64), np.empty(cap, np.float64)
+        rc, err = call(k, r, rd, cap)
+        arrs["n_pairs"] = int(n_pairs.value)
+        _lib.check(rc, err)
+        arrs.update(k=k[:arrs["n_pairs"]], r=r[:arrs["n_pairs"]], rd=rd[:arrs["n_pairs"]])
+        return arrs
+
     def run_device(self, ld_wind, maf, std_thr, rsq_thr, positions, table, *, own=None, flags=0):
         """As `run`, but the owned slice of the score table stays on the device: `table` is a float64 device
         tensor of shape (7, width) on this engine's GPU (rows l2, l2d, maf, residuals_std, l2_ws, l2d_ws, l2d_wse;

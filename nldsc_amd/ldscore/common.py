@@ -7,6 +7,7 @@ The reference's public names, validation rules and messages, 
   read_id_file, kept_individuals   --keep / --remove lists (FID IID per line) -> .fam line numbers (no reference
                          counterpart: PLINK's / LDSC's flags of the same names)
   AnnotFile              LDSC's .annot / .annot.gz (partitioned LD scores, --annot): names + an [M, C] float64 matrix
+  r2_adjusted            the adjusted r-squared of a correlation, in the engine's fp64 expression (--pairs-out)
   MAF, ResidualsSTDThreshold, RSQThreshold: [0, 1), [0, 1), [0, 0.1)
 (RSQThreshold's repr says `std_thr=`, as the reference's does.)
 """
@@ -22,7 +23,7 @@ from ..core.common import Data, NLDSCParameterError
 from ..core.logger import log
 
 __all__ = ["LDWindow", "PLINKFile", "BEDFile", "BIMFile", "FAMFile", "MAF", "ResidualsSTDThreshold",
-           "RSQThreshold", "NLDSCParameterError", "read_id_file", "kept_individuals", "AnnotFile"]
+           "RSQThreshold", "NLDSCParameterError", "read_id_file", "kept_individuals", "AnnotFile", "r2_adjusted"]
 
 # window metric -> (largest window, how the message names it)
 _WINDOW_LIMITS = {"bp": (5 * 10 ** 6, "5 Mbp"), "cm": (100, "100 cm")}
@@ -255,6 +256,14 @@ MAF = _threshold("MAF", "maf", 1.0, "Minor allele frequency must be between 0 an
 ResidualsSTDThreshold = _threshold("ResidualsSTDThreshold", "std_thr", 1.0,
                                    "standard deviation threshold must be between 0 and 1!")
 RSQThreshold = _threshold("RSQThreshold", "std_thr", 0.1, "r-squared threshold must be between 0 and 0.1!")
+
+
+def r2_adjusted(corr, n_org):
+    """1 - (1 - corr^2) (N - 1) / (N - 2) as the engine's pair epilogue forms it in fp64 (ld_kernels.hip R2Adj: the
+    factor (N - 1) / (N - 2) hoisted), for a correlation or an array of them; NaN stays NaN."""
+    c = np.asarray(corr, dtype=np.float64)
+    n = float(n_org)
+    return 1.0 - (1.0 - c * c) * ((n - 1.0) / (n - 2.0))
 
 
 def read_id_file(path: str) -> list:

@@ -20,8 +20,8 @@ from ..core.common import NLDSCParameterError, elapsed_time
 from ..core.logger import log
 from .common import (AnnotFile, FAMFile, BIMFile, LDWindow, MAF, ResidualsSTDThreshold, RSQThreshold,
                      kept_individuals)
-from .routine import (annot_output, m_annot_values, m_values, make_output, reject_sharded_annot, write_m_annot_file,
-                      write_m_file, write_scores)
+from .routine import (PAIRS_BUDGET, annot_output, m_annot_values, m_values, make_output, reject_pairs_options,
+                      reject_sharded_annot, run_pairs_to_file, write_m_annot_file, write_m_file, write_scores)
 
 CHROMS = [str(c) for c in range(1, 23)] + ["X", "Y", "XY", "MT"]
 
@@ -83,8 +83,11 @@ def _default_runner(device: int, keep=None, n_org_file: int = 0):
     if keep is not None:
         eng.set_keep(keep, n_org_file)
 
-    def run(bed_path: str, n_snp: int, n_org: int, ld_wind, maf, std_thr, rsq_thr, positions, flags, annot=None):
+    def run(bed_path: str, n_snp: int, n_org: int, ld_wind, maf, std_thr, rsq_thr, positions, flags, annot=None,
+            pairs=None):
         eng.load_bed_file(bed_path, n_snp, n_org)
+        if pairs is not None:  # (--pairs-out: dict(path, bim, min_r2, budget))
+            return run_pairs_to_file(eng, ld_wind, maf, std_thr, rsq_thr, positions, flags, **pairs), eng.timings()
         return eng.run(ld_wind, maf, std_thr, rsq_thr, positions, flags=flags, annot=annot), eng.timings()
     run.wants_path = True
     return run
@@ -96,12 +99,19 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
                         extra: bool = False, write_m: bool = False, flags: int = 0, device: int | None = None,
                         runner=None, rank: int | None = None, world: int | None = None,
                         progress: bool | None = None, keep: str | None = None,
-                        remove: str | None = None, annot: str | None = None) -> dict:
+                        remove: str | None = None, annot: str | None = None, pairs_out: str | None = None,
+                        pairs_min_r2: float | None = None, pairs_budget: int = PAIRS_BUDGET) -> dict:
     """Returns {chromosome: output DataFrame (None when written to `out`)} for the chromosomes this rank
     processed.  `keep` / `remove`: `FID IID` lists as in estimate_lds; every chromosome's .fam must resolve to the
     same individuals (a `runner` given by the caller then receives them as the keyword `keep`).  `annot`: an LDSC
     `.annot` / `.annot.gz` path with '@' in place of the chromosome, as in `bfile` (a runner then receives each
-    chromosome's [M, C] matrix as the keyword `annot`)."""
+    chromosome's [M, C] matrix as the keyword `annot`).  `pairs_out`: a path with '@' for each chromosome's pairwise
+    LD table, as in estimate_lds (a runner then receives dict(path, bim, min_r2, budget) as the keyword `pairs` and
+    writes the table itself)."""
+    if pairs_out is not None:
+        reject_pairs_options(annot)
+        if "@" not in pairs_out:
+            raise NLDSCParameterError("a whole-genome run needs '@' in --pairs-out (one pair table per chromosome)")
     if annot is not None:
         reject_sharded_annot()
         if "@" not in annot:
@@ -170,6 +180,9 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
         t0 = time.perf_counter()
         annot_ = AnnotFile(annot.replace("@", m["chrom"]), m["bim"]) if annot is not None else None
         annot_kw = {} if annot_ is None else {"annot": annot_.data}
+        if pairs_out is not None:
+            annot_kw["pairs"] = dict(path=pairs_out.replace("@", m["chrom"]), bim=m["bim"], min_r2=pairs_min_r2,
+                                     budget=pairs_budget)
         res, tim = runner(bed, n_snp, m["n_org"], ld_wind_.data, maf_thr_.data, std_thr_.data, rsq, m["pos"], flags,
                           **kept_kw, **annot_kw)
         ld = _Res(res)

@@ -19,10 +19,11 @@ from ..core.logger import log
 from . import _ldscore as lds
 from ..core.common import NLDSCParameterError
 from .common import (AnnotFile, BIMFile, LDWindow, MAF, PLINKFile, ResidualsSTDThreshold, RSQThreshold,
-                     kept_individuals)
+                     kept_individuals, r2_adjusted)
 
 __all__ = ["estimate_lds", "make_output", "format_scores", "write_scores", "show_summary", "m_values", "write_m_file",
-           "annot_output", "m_annot_values", "write_m_annot_file", "reject_sharded_annot"]
+           "annot_output", "m_annot_values", "write_m_annot_file", "reject_sharded_annot", "reject_pairs_options",
+           "PAIRS_HEADER", "PAIRS_BUDGET", "open_pairs", "write_pairs", "run_pairs_to_file"]
 
 
 def show_summary(ld) -> None:
@@ -136,6 +137,76 @@ def reject_sharded_annot() -> None:
                                   "with one rank (the ranks' tables are gathered without the per-annotation columns)")
 
 
+def reject_pairs_options(annot: str | None) -> None:
+    """--pairs-out with --annot (one band, one sink), or under torchrun with more than one rank (a rank's table would
+    cover its shard only)."""
+    if annot is not None:
+        raise NLDSCParameterError("--pairs-out and --annot cannot be combined: run them separately (an annotated "
+                                  "band and a pair table are different runs of the engine)")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NLDSCParameterError("--pairs-out (the pairwise LD table) runs on one GPU: launch it without torchrun, "
+                                  "or with one rank")
+
+
+# ---- the pairwise LD table (--pairs-out): one row per ordered pair (SNP_A, SNP_B) the run counts in WSA[SNP_A] ----
+PAIRS_HEADER = ("CHR", "SNP_A", "BP_A", "SNP_B", "BP_B", "R", "R2", "RD", "R2D")
+PAIRS_BUDGET = 32 * 1024 * 1024  # pairs per engine call (20 bytes each on the device, 36 in the host arrays)
+
+
+def open_pairs(path: str):
+    """A new pair table at `path` (gzip-compressed for a .gz suffix) with its header line; a text file object."""
+    import gzip
+    fh = gzip.open(path, "wt", newline="") if str(path).endswith(".gz") else open(path, "w", newline="")
+    fh.write("\t".join(PAIRS_HEADER) + "\n")
+    return fh
+
+
+def write_pairs(fh, bim: BIMFile, table: dict, own_begin: int, n_org: int) -> int:
+    """Append the rows of one owned range (a CSR table of Engine.run_pairs: row_ptr, k, r, rd; row 0 is SNP own_begin)
+    to the pair table `fh`: CHR SNP_A BP_A SNP_B BP_B R R2 RD R2D, tab-separated, floats "%.6f", NaN as an empty
+    field; R2 / R2D are r2_adjusted of R / RD for n_org individuals.  Returns the number of rows."""
+    row_ptr = np.asarray(table["row_ptr"], dtype=np.int64)
+    k = np.asarray(table["k"], dtype=np.int64)
+    if len(k) == 0:
+        return 0
+    j = own_begin + np.repeat(np.arange(len(row_ptr) - 1), np.diff(row_ptr))
+    snp, bp, chrom = bim.snp.to_numpy(), bim.bp.to_numpy(), bim.chr.to_numpy()
+    r, rd = np.asarray(table["r"], dtype=np.float64), np.asarray(table["rd"], dtype=np.float64)
+    df = pd.DataFrame({"CHR": chrom[j], "SNP_A": snp[j], "BP_A": bp[j], "SNP_B": snp[k], "BP_B": bp[k], "R": r,
+                       "R2": r2_adjusted(r, n_org), "RD": rd, "R2D": r2_adjusted(rd, n_org)})
+    df.to_csv(fh, sep="\t", index=False, header=False, float_format="%.6f", na_rep="")
+    return len(df)
+
+
+def run_pairs_to_file(engine, ld_wind, maf, std_thr, rsq_thr, positions, flags, *, path: str, bim: BIMFile,
+                      min_r2: float | None = None, budget: int = PAIRS_BUDGET, size_snps: int = 65536) -> dict:
+    """A run of the resident image that also writes its pair table to `path`: sizing calls over at most size_snps SNPs
+    each give the result arrays (bitwise a plain run's) and the table's row_ptr; the chromosome then goes in owned
+    ranges of at most `budget` pairs (_lib.pairs_split_ranges on that row_ptr), each appended to the file.  Returns
+    the result dict of Engine.run."""
+    from .. import _lib
+    n = engine.n_snp
+    args = (ld_wind, maf, std_thr, rsq_thr, positions)
+    res, row_ptr = None, [np.zeros(1, np.int64)]
+    for lo in range(0, n, size_snps):
+        hi = min(n, lo + size_snps)
+        s = engine.size_pairs(*args, own=(lo, hi), flags=flags, min_r2=min_r2)
+        if res is None:
+            res = {key: s[key] for key in ("l2", "l2d", "maf", "residuals_std", "l2_ws", "l2d_ws", "l2d_wse")}
+        else:
+            for key in res:
+                res[key][lo:hi] = s[key][lo:hi]
+        row_ptr.append(s["row_ptr"][1:] + row_ptr[-1][-1])
+    row_ptr = np.concatenate(row_ptr)
+    rows = 0
+    with open_pairs(path) as fh:
+        for lo, hi in _lib.pairs_split_ranges(row_ptr, budget):
+            t = engine._pairs(*args, (lo, hi), flags, min_r2, emit=True, cap=int(row_ptr[hi] - row_ptr[lo]))
+            rows += write_pairs(fh, bim, t, lo, engine.n_org)
+    log.info(f"Pair table: {rows:,} rows in {path}")
+    return res
+
+
 def m_values(bim: BIMFile, ld) -> tuple[int, int]:
     """M, MD as LDScoreReader derives them without an .M file (h2/common.py:128-130): rows
     surviving dropna + SNP de-duplication, and M * mean(WSDE / WSA)."""
@@ -217,11 +288,17 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
                  rsq_thr: float | None = None, *, out: str | None = None, extra: bool = False, summary: bool = False,
                  verbose: int = 0, write_m: bool = False, flags: int = 0, device: int | None = None,
                  progress: bool | None = None, keep: str | None = None, remove: str | None = None,
-                 annot: str | None = None):
-    """`keep` / `remove`: paths of `FID IID` lists (PLINK's / LDSC's --keep, --remove): the scores are computed on the
+                 annot: str | None = None, pairs_out: str | None = None, pairs_min_r2: float | None = None,
+                 pairs_budget: int = PAIRS_BUDGET):
+    """`pairs_out`: also write the pairwise LD table behind the scores there (write_pairs; `.gz` compresses), with
+    `pairs_min_r2` only the pairs whose R2 or R2D exceeds it, in engine calls of at most `pairs_budget` pairs; the
+    scores are the same, bit for bit.
+    `keep` / `remove`: paths of `FID IID` lists (PLINK's / LDSC's --keep, --remove): the scores are computed on the
     .fam lines of the first minus those of the second, in PLINK's sample order (common.kept_individuals).
     `annot`: path of an LDSC `.annot` / `.annot.gz` file (common.AnnotFile): partitioned LD scores, the table gains
     L2_<name> and L2D_<name> columns and `write_m` also writes `<out>.M_annot`."""
+    if pairs_out is not None:
+        reject_pairs_options(annot)
     if annot is not None:
         reject_sharded_annot()
     bed_, bim_, fam_ = PLINKFile.parse(bfile)
@@ -255,7 +332,14 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
     bar = Progress(bim_.n_snp, "SNPs", enabled=progress)
     bar.update(0, "reading the .bed and computing on the GPU", force=True)
     dist = _process_group()
-    if dist is None:
+    if pairs_out is not None:  # the engine itself: one load, the sizing and emitting calls of every owned range
+        from .genome import _default_runner
+        run = _default_runner(-1 if device is None else int(device), kept, fam_.n_org)
+        res, _ = run(bed_.data, bim_.n_snp, fam_.n_org, ld_wind_.data, maf_thr_.data, std_thr_.data, rsq_thr_.data,
+                     np.asarray(params.positions, dtype=np.float64), int(flags),
+                     pairs=dict(path=pairs_out, bim=bim_, min_r2=pairs_min_r2, budget=pairs_budget))
+        ld = _Result(res)
+    elif dist is None:
         ld = lds.calculate(params)
     else:  # torchrun: position-sharded over the ranks' GPUs, tables gathered on rank 0
         ld = _calculate_sharded(dist, params)
