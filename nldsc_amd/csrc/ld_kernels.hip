@@ -1241,6 +1241,20 @@ struct SnpSlot {
     int L, R, fl, g;
 };
 
+// SNP g's slot; a slot past the last SNP (the ragged last block) has an empty window and no flags: no pair needs it
+__device__ __forceinline__ SnpSlot load_slot(int g, const double* __restrict__ pos, const int* __restrict__ Lw,
+                                             const int* __restrict__ Rw, const uint8_t* __restrict__ sflags,
+                                             int n_snp) {
+    SnpSlot si;
+    si.g = g;
+    if (g < n_snp) {
+        si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
+    } else {
+        si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
+    }
+    return si;
+}
+
 __device__ __forceinline__ double r2_adjusted(double dot, double n) {
     // Math::r2_adjusted (tools.h:87-92)
     const double corr = dot * (1. / n);
@@ -1361,14 +1375,7 @@ __device__ __forceinline__ void band_body(BandLds& sh, const int4 it, const uint
         tab[1][s] = make_float2(l01.z, l01.w);
         tab[2][s] = make_float2(l23.x, l23.y);
         tab[3][s] = make_float2(l23.z, l23.w);
-        SnpSlot si;
-        si.g = g;
-        if (g < n_snp) {
-            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
-        } else {
-            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
-        }
-        info[s] = si;
+        info[s] = load_slot(g, pos, Lw, Rw, sflags, n_snp);
     }
     __syncthreads();
 
@@ -1582,6 +1589,24 @@ __device__ __forceinline__ PairNeed pair_need(const SnpSlot& ci, const SnpSlot& 
     return n;
 }
 
+// What a consumer of the single pairs sees of pair_epilogue's loop (the annotated and the pairs epilogue kernels have
+// one each; the hooks observe values and change none).  Per lane and register r, in this order:
+//   begin(r, si)                       before the pair's masks (si: the row SNP's slot);
+//   additive(r, nij, nji, aa, r2)      the pair is evaluated: the additive dot and its r2adj;
+//   dom_row(r, ar, rd)                 the row SNP's dominance term is taken (A_i . R_j), dom_col(r, ra, rd) the
+//                                      column SNP's (R_i . A_j);
+//   end(r)                             after the pair, evaluated or not.
+// BOTH_ORDERS: a diagonal item's pair above the diagonal is evaluated where the one below it is needed (its mirror
+// serves both).  SUMS = false drops the per-SNP sums: no reduction, nothing added to the accumulators.
+struct NoSink {
+    static constexpr bool BOTH_ORDERS = false, SUMS = true;
+    __device__ __forceinline__ constexpr void begin(int, int) const {}
+    __device__ __forceinline__ constexpr void additive(int, bool, bool, double, double) const {}
+    __device__ __forceinline__ constexpr void dom_row(int, double, double) const {}
+    __device__ __forceinline__ constexpr void dom_col(int, double, double) const {}
+    __device__ __forceinline__ constexpr void end(int) const {}
+};
+
 // Epilogue of one 32x32 block pair (row slots rb.., column slots cb.. of the slot tables `info` / `cst`):
 // standardised dots from the 8 integer Gram entries in fp64, r2adj, window/pointer masks, and the pair's
 // per-SNP sums (ldscalc.h:33-55), reduced across the wave in registers (reduce_rows4) and added to the per-SNP
@@ -1589,14 +1614,16 @@ __device__ __forceinline__ PairNeed pair_need(const SnpSlot& ci, const SnpSlot& 
 // MB: the Gram is in the missing basis {x, h, m} (fp4 path): gxo holds x.m, gox m.x, goo m.m, goh m.h,
 // gho h.m, and `kslots` is the number of individual slots (n_org; the other slots are all-zero in every
 // plane); o = 1 - m over the individual slots.
-template <bool DOM, class Acc, bool MB = false, bool KC = false>
+// sink: a consumer of the single pairs (NoSink above: none), its type deduced from the argument.
+template <bool DOM, class Acc, bool MB = false, bool KC = false, class Sink = NoSink>
 __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpConst* cst, int rb, int cb, bool diag,
                                               int i, int h, const Acc& gxx, const Acc& gxo, const Acc& gox,
                                               const Acc& goo, const Acc& gxh, const Acc& goh, const Acc& ghx,
                                               const Acc& gho, double ld_wind, double n_org, double rsq_thr,
                                               double kslots, int own_lo, int own_hi, int n_snp,
                                               double* __restrict__ l2_acc, double* __restrict__ l2d_acc,
-                                              int* __restrict__ ws_acc) {
+                                              int* __restrict__ ws_acc, Sink&& sink = Sink{}) {
+    using S = std::remove_reference_t<Sink>;
     const R2Adj r2adj(n_org);
     const int sj = cb + i;
     const SnpSlot cj = info[sj];
@@ -1615,8 +1642,10 @@ __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpCons
             const bool rpi = (ci.fl & 2) != 0;
             const PairNeed need = pair_need(ci, cj, diag, ld_wind);
             const bool nij = need.nij, nji = need.nji;
+            const bool nrev = S::BOTH_ORDERS && diag && si - rb < i && pair_need(cj, ci, true, ld_wind).nij;
             SlotSum rv = {0.0, 0.0, 0};
-            if (nij || nji) {
+            sink.begin(r, si);
+            if (nij || nji || nrev) {
                 const SnpConst ki = cst[si];
                 // MB: the fp4 Gram is over v = m + 2x (the raw 2-bit code placed as an e2m1 value), h and m:
                 // x.x = (v.v - v.m - m.v + m.m) / 4, x.m = (v.m - m.m) / 2, m.x = (m.v - m.m) / 2 (exact)
@@ -1630,6 +1659,7 @@ __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpCons
                 const double aa = (xx - kj.mu * xo - ki.mu * (ox - kj.mu * oo)) * (ki.isa * kj.isa) +
                                   (KC ? kj.ka * ki.SA + ki.ka * (kj.SA + kj.ka * n_org) : 0.0);
                 const double r2 = r2adj(aa);
+                sink.additive(r, nij, nji, aa, r2);
                 if (nij) { rv.l2 = r2; rv.cnt = 1; }
                 if (nji) { col.l2 += r2; col.cnt += 1; }
                 if (DOM) {
@@ -1642,6 +1672,7 @@ __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpCons
                         const double rd = r2adj(ar);
                         rv.l2d = rd;
                         rv.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
+                        sink.dom_row(r, ar, rd);
                     }
                     if (!diag && nji && rpi) {  // R_i . A_j -> L2D_j
                         const double hx = MB ? 0.5 * ((double)ghx[r] - (double)gho[r]) : (double)ghx[r];
@@ -1652,20 +1683,26 @@ __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpCons
                         const double rd = r2adj(ra);
                         col.l2d += rd;
                         col.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
+                        sink.dom_col(r, ra, rd);
                     }
                 }
             }
             rowv[k] = rv;
+            sink.end(r);
         }
-        const SlotSum t = reduce_rows4(rowv, i);  // lanes i >> 3 == k: row rb + k + 8q + 4h
-        if ((i & 7) == q) {
-            mine = t;
-            my_row = rb + (i >> 3) + 8 * q + 4 * h;
+        if constexpr (S::SUMS) {
+            const SlotSum t = reduce_rows4(rowv, i);  // lanes i >> 3 == k: row rb + k + 8q + 4h
+            if ((i & 7) == q) {
+                mine = t;
+                my_row = rb + (i >> 3) + 8 * q + 4 * h;
+            }
         }
     }
-    col = col + xlane<32>(col);  // the partner lane (i, 1 - h) holds the other 16 rows of column i
-    if (my_row >= 0) flush_slot(info[my_row], mine, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
-    if (h == 0) flush_slot(cj, col, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
+    if constexpr (S::SUMS) {
+        col = col + xlane<32>(col);  // the partner lane (i, 1 - h) holds the other 16 rows of column i
+        if (my_row >= 0) flush_slot(info[my_row], mine, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
+        if (h == 0) flush_slot(cj, col, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
+    }
 }
 
 // Items holding a rare variant whose vectors are the reference's fp32 ones (ka / kr != 0: blk_rep[block] = 1,
@@ -1679,10 +1716,12 @@ __device__ __forceinline__ bool skip_item(const uint8_t* blk_rep, int4 it) {
     return KC ? !rep : rep;
 }
 
-struct BandI8Lds {
-    SnpSlot info[NS_MAX];
-    SnpConst cst[NS_MAX];
+template <int NS>
+struct SlotLds {
+    SnpSlot info[NS];
+    SnpConst cst[NS];
 };
+typedef SlotLds<NS_MAX> BandI8Lds;
 
 // NC column blocks J0 .. J0+NC-1 share the row decode; DIAG0: block 0 is the diagonal (J0 == I).
 template <bool DOM, int NC, bool DIAG0, bool KC>
@@ -1699,14 +1738,7 @@ __device__ __forceinline__ void band_i8_body(BandI8Lds& sh, const int4 it, const
     const int I = it.x, J0 = it.y;
     for (int s = lane; s < NS; s += 64) {
         const int g = s < 32 ? I * 32 + s : (J0 + (s - 32) / 32) * 32 + (s & 31);
-        SnpSlot si;
-        si.g = g;
-        if (g < n_snp) {
-            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
-        } else {
-            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
-        }
-        sh.info[s] = si;
+        sh.info[s] = load_slot(g, pos, Lw, Rw, sflags, n_snp);
         sh.cst[s] = cst[g];
     }
     __syncthreads();
@@ -1932,14 +1964,7 @@ __device__ __forceinline__ void band_f4_body(BandI8Lds& sh, const int4 it, const
     const int I = it.x, J0 = it.y;
     for (int s = lane; s < NS; s += 64) {
         const int g = s < 32 ? I * 32 + s : (J0 + (s - 32) / 32) * 32 + (s & 31);
-        SnpSlot si;
-        si.g = g;
-        if (g < n_snp) {
-            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
-        } else {
-            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
-        }
-        sh.info[s] = si;
+        sh.info[s] = load_slot(g, pos, Lw, Rw, sflags, n_snp);
         sh.cst[s] = cst[g];
     }
     __syncthreads();
@@ -2297,14 +2322,7 @@ __global__ void __launch_bounds__(256, 2) band_f4_t2_kernel(
     if (tid < T2_SLOTS) {
         const int blk = (tid < 64 ? 2 * I2 : 2 * J2) + ((tid >> 5) & 1);
         const int g = blk * 32 + (tid & 31);
-        SnpSlot si;
-        si.g = g;
-        if (g < n_snp) {
-            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
-        } else {
-            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
-        }
-        sh.info[tid] = si;
+        sh.info[tid] = load_slot(g, pos, Lw, Rw, sflags, n_snp);
         sh.cst[tid] = blk < nblk ? cst[g] : SnpConst{};
     }
     const int rb = 2 * I2 + (w >> 1), cb = 2 * J2 + (w & 1);
@@ -2466,14 +2484,7 @@ __global__ void __launch_bounds__(256, 1) band_f4_q_kernel(
     {
         const int b = strip_blk(tid >> 5);
         const int g = b * 32 + (tid & 31);
-        SnpSlot si;
-        si.g = g;
-        if (g < n_snp) {
-            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
-        } else {
-            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
-        }
-        sh.info[tid] = si;
+        sh.info[tid] = load_slot(g, pos, Lw, Rw, sflags, n_snp);
         sh.cst[tid] = b < nblk ? cst[g] : SnpConst{};
     }
     // this wave's block pairs p = 2a + b: row block 4 I4 + 2 (w >> 1) + a, column block 4 J4 + 2 (w & 1) + b
@@ -2789,6 +2800,44 @@ __global__ void __launch_bounds__(64, 2) band_f4_part_kernel(const uint32_t* __r
 #undef NLDSC_BODY
 }
 
+// How every K-split epilogue kernel (one wave per item) starts on item `it` = items[blockIdx.x]: the 64 slots (the
+// SNPs of block it.x, then of it.y) to info / scst; the item's P partial Gram tiles summed in piece order into g8
+// (x.x, x.m, m.x, m.m, x.h, m.h, h.x, h.m); a diagonal item's m.x = (x.m)^T through `tr` (32 x 33 floats).
+// Returns the lane's own slot.
+__device__ __forceinline__ SnpSlot load_split_item(SnpSlot* info, SnpConst* scst, float* tr, f32x16v (&g8)[8],
+                                                   const int4 it, const SnpConst* __restrict__ cst,
+                                                   const double* __restrict__ pos, const int* __restrict__ Lw,
+                                                   const int* __restrict__ Rw, const uint8_t* __restrict__ sflags,
+                                                   int n_snp, int P, const float* __restrict__ gram) {
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int g = lane < 32 ? it.x * 32 + lane : it.y * 32 + (lane & 31);
+    const SnpSlot slot = load_slot(g, pos, Lw, Rw, sflags, n_snp);
+    info[lane] = slot;
+    scst[lane] = cst[g];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) g8[t] = f32x16v{};
+    const float* src = gram + (size_t)blockIdx.x * P * 8192 + lane * 16;
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const float4* q = reinterpret_cast<const float4*>(src + (size_t)p * 8192 + t * 1024);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 v = q[k];
+                g8[t][4 * k] += v.x; g8[t][4 * k + 1] += v.y; g8[t][4 * k + 2] += v.z; g8[t][4 * k + 3] += v.w;
+            }
+        }
+    __syncthreads();
+    if (it.x == it.y) {  // m.x(a, b) = x.m(b, a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = g8[1][r];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) g8[2][r] = tr[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
+    }
+    return slot;
+}
+
 template <bool DOM, bool KC>
 __global__ void __launch_bounds__(64, 2) band_f4_epi_kernel(const SnpConst* __restrict__ cst,
                                                           const int4* __restrict__ items,
@@ -2811,42 +2860,9 @@ __global__ void __launch_bounds__(64, 2) band_f4_epi_kernel(const SnpConst* __re
     if (count == nullptr && skip_item<KC>(blk_rep, it)) return;
     if (blk_miss != nullptr && routed_item(blk_miss, route_shift, it.x, it.y, (n_snp + 31) >> 5)) return;
     const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    const int I = it.x, J = it.y;
-    const bool diag = I == J;
-    for (int s = lane; s < 64; s += 64) {
-        const int g = s < 32 ? I * 32 + s : J * 32 + (s & 31);
-        SnpSlot si;
-        si.g = g;
-        if (g < n_snp) {
-            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
-        } else {
-            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
-        }
-        sh.info[s] = si;
-        sh.cst[s] = cst[g];
-    }
     f32x16v g8[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) g8[t] = f32x16v{};
-    const float* src = gram + (size_t)blockIdx.x * P * 8192 + lane * 16;
-    for (int p = 0; p < P; ++p)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const float4* q = reinterpret_cast<const float4*>(src + (size_t)p * 8192 + t * 1024);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float4 v = q[k];
-                g8[t][4 * k] += v.x; g8[t][4 * k + 1] += v.y; g8[t][4 * k + 2] += v.z; g8[t][4 * k + 3] += v.w;
-            }
-        }
-    __syncthreads();
-    if (diag) {  // m.x(a, b) = x.m(b, a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = g8[1][r];
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) g8[2][r] = tr[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
-    }
+    load_split_item(sh.info, sh.cst, tr, g8, it, cst, pos, Lw, Rw, sflags, n_snp, P, gram);
+    const bool diag = it.x == it.y;
     pair_epilogue<DOM, f32x16v, true, KC>(sh.info, sh.cst, 0, 32, diag, i, h, g8[0], g8[1], g8[2], g8[3], g8[4], g8[5],
                                           g8[6], g8[7], ld_wind, n_org, rsq_thr, n_org, own_lo, own_hi, n_snp, l2_acc,
                                           l2d_acc, ws_acc);
@@ -2854,23 +2870,18 @@ __global__ void __launch_bounds__(64, 2) band_f4_epi_kernel(const SnpConst* __re
 
 // ---- partitioned LD scores: L2[j, c] = sum_k a[k, c] r2adj(j, k) per annotation column c (and the dominance sum) ----
 // An annotated run sends every block pair through band_f4_part_kernel (exact Gram tiles to memory) and then through
-// band_f4_epi_annot_kernel, which is band_f4_epi_kernel plus the per-annotation sums: the pair loop below is
-// pair_epilogue<DOM, f32x16v, true, KC> expression for expression (the seven ordinary arrays are bitwise those of a
-// plain run) and keeps each pair's masked r2 values in an LDS tile; the annotations then go by in chunks of
-// ANNOT_CHUNK columns whose weights for the item's 64 slots are staged through LDS, each column's four weighted sums
-// reduced with reduce_rows4 / xlane in the plain epilogue's order and added to category-major fixed-point
-// accumulators acc[c * n_snp + g] in units of 1 / ascale[c] (= 2^(-44 + e_c), band_plan.h annot_scale_exp: a SNP's
-// total stays below 2^63 for |a| <= 2^e_c) with 64-bit integer atomics: order-independent, bit-reproducible.  What
-// that rounding drops of an item's partial goes, in units of 2^-40 of the first, to a second accumulator of the same
-// layout (|residual| <= 2^39 per item, fewer than 2^20 items per SNP), so a total carries the fp64 partials'
-// own precision: a column and a multiple of it then agree to the rounding of their fp64 products, whatever e_c.
+// band_f4_epi_annot_kernel, which is band_f4_epi_kernel plus the per-annotation sums: it runs the same pair_epilogue
+// (the seven ordinary arrays are a plain run's by construction) with AnnotSink as its sink, which keeps each pair's
+// masked r2 values in an LDS tile; the annotations then go by in chunks of ANNOT_CHUNK columns whose weights for the
+// item's 64 slots are staged through LDS, each column's four weighted sums reduced with reduce_rows4 / xlane in the
+// plain epilogue's order and added to category-major fixed-point accumulators acc[c * n_snp + g] in units of
+// 1 / ascale[c] (= 2^(-44 + e_c), band_plan.h annot_scale_exp: a SNP's total stays below 2^63 for |a| <= 2^e_c) with
+// 64-bit integer atomics: order-independent, bit-reproducible.  What that rounding drops of an item's partial goes,
+// in units of 2^-40 of the first, to a second accumulator of the same layout (|residual| <= 2^39 per item, fewer
+// than 2^20 items per SNP), so a total carries the fp64 partials' own precision: a column and a multiple of it then
+// agree to the rounding of their fp64 products, whatever e_c.
 constexpr int ANNOT_CHUNK = 16;
 constexpr double ANNOT_LO_SCALE = 1099511627776.0;  // 2^40
-
-struct AnnotSlots {
-    SnpSlot info[64];
-    SnpConst cst[64];
-};
 
 // One slot's weighted sum of one work item and one annotation -> that annotation's per-SNP total.  Exact zeros (an
 // annotation without a member among the other block's SNPs: binary annotations are mostly zero) add nothing; a
@@ -2886,6 +2897,32 @@ __device__ __forceinline__ void flush_annot(int g, double v, double scale, int o
     if (lo != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&acc_lo[g]), (unsigned long long)lo);
 }
 
+// pair_epilogue's sink of the annotated epilogue: the masked r2 of the lane's 16 pairs to the LDS tile pv, [0]
+// nij ? r2 : 0 (the row SNP's additive term), [1] nji ? r2 : 0 (the column SNP's), [2], [3] the dominance terms of the
+// row / column SNP; each lane reads back only what it wrote.
+template <bool DOM>
+struct AnnotSink {
+    static constexpr bool BOTH_ORDERS = false, SUMS = true;
+    double (*pv)[16][64];
+    int lane;
+    double p_row, p_col, d_row, d_col;  // the pair at hand
+    __device__ __forceinline__ void begin(int, int) { p_row = p_col = d_row = d_col = 0.0; }
+    __device__ __forceinline__ void additive(int, bool nij, bool nji, double, double r2) {
+        if (nij) p_row = r2;
+        if (nji) p_col = r2;
+    }
+    __device__ __forceinline__ void dom_row(int, double, double rd) { d_row = rd; }
+    __device__ __forceinline__ void dom_col(int, double, double rd) { d_col = rd; }
+    __device__ __forceinline__ void end(int r) {
+        pv[0][r][lane] = p_row;
+        pv[1][r][lane] = p_col;
+        if (DOM) {
+            pv[2][r][lane] = d_row;
+            pv[3][r][lane] = d_col;
+        }
+    }
+};
+
 // (no waves-per-SIMD bound: the 37 / 53 KiB of LDS hold the kernel to 4 / 3 workgroups per CU, and the plain
 // epilogue's registers beside the kept r2 values need more than the 256 a second wave per SIMD would leave)
 template <bool DOM, bool KC>
@@ -2897,134 +2934,24 @@ __global__ void __launch_bounds__(64) band_f4_epi_annot_kernel(
     const float* __restrict__ gram, const double* __restrict__ annot, const double* __restrict__ ascale, int n_annot,
     double* __restrict__ l2c_acc, double* __restrict__ l2dc_acc, double* __restrict__ l2c_lo,
     double* __restrict__ l2dc_lo) {
-    __shared__ AnnotSlots sh;
+    __shared__ SlotLds<64> sh;
     __shared__ float tr[32 * 33];
-    // masked r2 of the lane's 16 pairs: [0] nij ? r2 : 0 (row SNP's additive term), [1] nji ? r2 : 0 (column SNP's),
-    // [2], [3] the dominance terms of the row / column SNP; each lane reads back only what it wrote
-    __shared__ double pv[DOM ? 4 : 2][16][64];
+    __shared__ double pv[DOM ? 4 : 2][16][64];  // AnnotSink's tile
     __shared__ double wt[ANNOT_CHUNK][64];  // a chunk's weights of the 64 slots
     const int4 it = items[blockIdx.x];
     if (skip_item<KC>(blk_rep, it)) return;
     const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    const int I = it.x, J = it.y;
-    const bool diag = I == J;
-    {
-        const int s = lane;
-        const int g = s < 32 ? I * 32 + s : J * 32 + (s & 31);
-        SnpSlot si;
-        si.g = g;
-        if (g < n_snp) {
-            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
-        } else {
-            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
-        }
-        sh.info[s] = si;
-        sh.cst[s] = cst[g];
-    }
     f32x16v g8[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) g8[t] = f32x16v{};
-    const float* src = gram + (size_t)blockIdx.x * P * 8192 + lane * 16;
-    for (int p = 0; p < P; ++p)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const float4* q = reinterpret_cast<const float4*>(src + (size_t)p * 8192 + t * 1024);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float4 v = q[k];
-                g8[t][4 * k] += v.x; g8[t][4 * k + 1] += v.y; g8[t][4 * k + 2] += v.z; g8[t][4 * k + 3] += v.w;
-            }
-        }
-    __syncthreads();
-    if (diag) {  // m.x(a, b) = x.m(b, a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = g8[1][r];
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) g8[2][r] = tr[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
-    }
-    // ---- the plain epilogue (pair_epilogue, MB basis), each pair's r2 values kept ----
+    load_split_item(sh.info, sh.cst, tr, g8, it, cst, pos, Lw, Rw, sflags, n_snp, P, gram);
+    // ---- the plain epilogue, each pair's r2 values kept ----
+    AnnotSink<DOM> sink{pv, lane};
+    pair_epilogue<DOM, f32x16v, true, KC>(sh.info, sh.cst, 0, 32, it.x == it.y, i, h, g8[0], g8[1], g8[2], g8[3], g8[4],
+                                          g8[5], g8[6], g8[7], ld_wind, n_org, rsq_thr, n_org, own_lo, own_hi, n_snp,
+                                          l2_acc, l2d_acc, ws_acc, sink);
+    // ---- the per-annotation sums: the same four sums, each pair weighted by the other SNP's annotation value ----
     const SnpSlot* info = sh.info;
-    const f32x16v &gxx = g8[0], &gxo = g8[1], &gox = g8[2], &goo = g8[3], &gxh = g8[4], &goh = g8[5], &ghx = g8[6],
-                  &gho = g8[7];
-    const double kslots = n_org;
-    const R2Adj r2adj(n_org);
     const int sj = 32 + i;
     const SnpSlot cj = info[sj];
-    {
-        const SnpConst kj = sh.cst[sj];
-        const bool rpj = (cj.fl & 2) != 0;
-        SlotSum col = {0.0, 0.0, 0}, mine = {0.0, 0.0, 0};
-        int my_row = -1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {  // row group q: registers r = 4q + k, rows k + 8q + 4h
-            SlotSum rowv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = 4 * q + k;
-                const int si = k + 8 * q + 4 * h;
-                const SnpSlot ci = info[si];
-                const bool rpi = (ci.fl & 2) != 0;
-                const PairNeed need = pair_need(ci, cj, diag, ld_wind);
-                const bool nij = need.nij, nji = need.nji;
-                SlotSum rv = {0.0, 0.0, 0};
-                double p_row = 0.0, p_col = 0.0, d_row = 0.0, d_col = 0.0;
-                if (nij || nji) {
-                    const SnpConst ki = sh.cst[si];
-                    const double mm = (double)goo[r];
-                    const double xx = 0.25 * ((double)gxx[r] - (double)gxo[r] - (double)gox[r] + mm);
-                    const double xo = ki.X - 0.5 * ((double)gxo[r] - mm);
-                    const double ox = kj.X - 0.5 * ((double)gox[r] - mm);
-                    const double oo = ki.Ob + kj.Ob - kslots + mm;
-                    const double aa = (xx - kj.mu * xo - ki.mu * (ox - kj.mu * oo)) * (ki.isa * kj.isa) +
-                                      (KC ? kj.ka * ki.SA + ki.ka * (kj.SA + kj.ka * n_org) : 0.0);
-                    const double r2 = r2adj(aa);
-                    if (nij) { rv.l2 = r2; rv.cnt = 1; p_row = r2; }
-                    if (nji) { col.l2 += r2; col.cnt += 1; p_col = r2; }
-                    if (DOM) {
-                        if (nij && rpj) {  // A_i . R_j -> L2D_i
-                            const double xh = 0.5 * ((double)gxh[r] - (double)goh[r]);
-                            const double oh = kj.H - (double)goh[r];
-                            const double ar = (2.0 * xh - kj.beta * xx - kj.c * xo -
-                                               ki.mu * (2.0 * oh - kj.beta * ox - kj.c * oo)) * (ki.isa * kj.is) +
-                                              (KC ? kj.kr * ki.SA + ki.ka * (kj.SR + kj.kr * n_org) : 0.0);
-                            const double rd = r2adj(ar);
-                            rv.l2d = rd;
-                            rv.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
-                            d_row = rd;
-                        }
-                        if (!diag && nji && rpi) {  // R_i . A_j -> L2D_j
-                            const double hx = 0.5 * ((double)ghx[r] - (double)gho[r]);
-                            const double ho = ki.H - (double)gho[r];
-                            const double ra = (2.0 * hx - ki.beta * xx - ki.c * ox -
-                                               kj.mu * (2.0 * ho - ki.beta * xo - ki.c * oo)) * (ki.is * kj.isa) +
-                                              (KC ? ki.kr * kj.SA + kj.ka * (ki.SR + ki.kr * n_org) : 0.0);
-                            const double rd = r2adj(ra);
-                            col.l2d += rd;
-                            col.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
-                            d_col = rd;
-                        }
-                    }
-                }
-                rowv[k] = rv;
-                pv[0][r][lane] = p_row;
-                pv[1][r][lane] = p_col;
-                if (DOM) {
-                    pv[2][r][lane] = d_row;
-                    pv[3][r][lane] = d_col;
-                }
-            }
-            const SlotSum t = reduce_rows4(rowv, i);  // lanes i >> 3 == k: row k + 8q + 4h
-            if ((i & 7) == q) {
-                mine = t;
-                my_row = (i >> 3) + 8 * q + 4 * h;
-            }
-        }
-        col = col + xlane<32>(col);  // the partner lane (i, 1 - h) holds the other 16 rows of column i
-        if (my_row >= 0) flush_slot(info[my_row], mine, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
-        if (h == 0) flush_slot(cj, col, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
-    }
-    // ---- the per-annotation sums: the same four sums, each pair weighted by the other SNP's annotation value ----
     const int my_q = i & 7;  // lanes with my_q < 4 end reduce_rows4 of row group my_q with a row's total
     const int g_row = my_q < 4 ? info[(i >> 3) + 8 * my_q + 4 * h].g : n_snp;
     for (int c0 = 0; c0 < n_annot; c0 += ANNOT_CHUNK) {
@@ -3096,10 +3023,10 @@ __global__ void __launch_bounds__(256) finalize_annot_kernel(
 }
 
 // ---- the pairwise LD table: the (k, r, rd) of every ordered pair (j, k) the plain run counts in WSA[j] ----
-// A pairs run sends every block pair through band_f4_part_kernel and then through band_f4_epi_pairs_kernel, the annotated
-// epilogue's pair loop (pair_epilogue<DOM, f32x16v, true, KC> expression for expression: with EMIT = false it adds
-// the ordinary sums, bitwise a plain run's) with the pairs themselves as its sink, in CSR over the owned SNPs, each
-// row sorted by k, no position decided by an atomic:
+// A pairs run sends every block pair through band_f4_part_kernel and then through band_f4_epi_pairs_kernel, which runs
+// the plain epilogue's pair_epilogue with PairsSink as its sink (with EMIT = false it adds the ordinary sums, a plain
+// run's by construction) and writes the pairs the sink kept, in CSR over the owned SNPs, each row sorted by k, no
+// position decided by an atomic:
 //   count (EMIT = false): every owned slot SNP g's kept entries against the item's other block nb, stored plainly to
 //     the dense cnt[pairs_cell(g, nb)] (band_plan.h; one item produces each cell: the item of g's block and nb);
 //   scan (pairs_row_scan_kernel + the host's 64-bit prefix over the row lengths): each cell's offset in its row and
@@ -3113,7 +3040,37 @@ __global__ void __launch_bounds__(256) finalize_annot_kernel(
 // and r(k, j) are the same bits everywhere.  Signs are those of the file's coding: a row stored flipped (flip[j]:
 // 00 <-> 11 swapped at load) has A negated and R unchanged (snp_stats_kernel), except a replayed rare variant, whose
 // constants describe the reference's vectors of the file's coding (reference_residual_kernel; KC items only), so
-// r takes the product of both SNPs' signs and rd the sign of the SNP whose A it holds.  min_r2 (NaN: off) keeps an entry when r2adj(r) or r2adj(rd) exceeds it.
+// r takes the product of both SNPs' signs and rd the sign of the SNP whose A it holds.  min_r2 (NaN: off) keeps an
+// entry when r2adj(r) or r2adj(rd) exceeds it.
+
+// pair_epilogue's sink of the pairs epilogue, the lane's 16 pairs: r (va), rd of the row SNP's entry (A_i . R_j:
+// vd_row) and of the column SNP's (R_i . A_j: vd_col), NaN where not taken, and which of the 16 the row SNP (bit r of
+// m_row: nij) and the column SNP (m_col: nji) need.  ssgn: the 64 slots' signs, sgj the lane's column SNP's.
+template <bool EMIT>
+struct PairsSink {
+    static constexpr bool BOTH_ORDERS = true, SUMS = !EMIT;
+    const double* ssgn;
+    double inv_n, sgj;
+    double va[16], vd_row[16], vd_col[16];
+    unsigned m_row, m_col;
+    int si;      // the pair at hand: its row slot
+    double sgi;  // and that slot's sign
+    __device__ __forceinline__ void begin(int r, int si_) {
+        si = si_;
+        va[r] = 0.0;
+        vd_row[r] = vd_col[r] = __builtin_nan("");
+    }
+    __device__ __forceinline__ void additive(int r, bool nij, bool nji, double aa, double) {
+        sgi = ssgn[si];
+        va[r] = aa * inv_n * (sgi * sgj);
+        if (nij) m_row |= 1u << r;
+        if (nji) m_col |= 1u << r;
+    }
+    __device__ __forceinline__ void dom_row(int r, double ar, double) { vd_row[r] = ar * inv_n * sgi; }
+    __device__ __forceinline__ void dom_col(int r, double ra, double) { vd_col[r] = ra * inv_n * sgj; }
+    __device__ __forceinline__ void end(int) {}
+};
+
 template <bool DOM, bool KC, bool EMIT>
 __global__ void __launch_bounds__(64) band_f4_epi_pairs_kernel(
     const SnpConst* __restrict__ cst, const int4* __restrict__ items, const double* __restrict__ pos,
@@ -3123,7 +3080,7 @@ __global__ void __launch_bounds__(64) band_f4_epi_pairs_kernel(
     const float* __restrict__ gram, int* __restrict__ cnt, int Wb, const long long* __restrict__ row_ptr,
     long long n_pairs, int* __restrict__ out_k, double* __restrict__ out_r, double* __restrict__ out_rd,
     double min_r2, const uint8_t* __restrict__ flip, const int* __restrict__ counts) {
-    __shared__ AnnotSlots sh;
+    __shared__ SlotLds<64> sh;
     __shared__ double ssgn[64];  // per slot: -1 where the stored A is the file's negated
     __shared__ float tr[32 * 33];
     __shared__ double trd[32 * 33];
@@ -3135,135 +3092,29 @@ __global__ void __launch_bounds__(64) band_f4_epi_pairs_kernel(
     const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
     const int I = it.x, J = it.y;
     const bool diag = I == J;
+    f32x16v g8[8];
     {
         const int s = lane;
-        const int g = s < 32 ? I * 32 + s : J * 32 + (s & 31);
-        SnpSlot si;
-        si.g = g;
-        if (g < n_snp) {
-            si.pos = pos[g]; si.L = Lw[g]; si.R = Rw[g]; si.fl = sflags[g];
-        } else {
-            si.pos = 0.0; si.L = -1; si.R = -2; si.fl = 0;
-        }
-        sh.info[s] = si;
-        sh.cst[s] = cst[g];
+        const SnpSlot si = load_split_item(sh.info, sh.cst, tr, g8, it, cst, pos, Lw, Rw, sflags, n_snp, P, gram);
+        const int g = si.g;
         long long cell = g < n_snp && !(diag && s >= 32) ? pairs_cell(g, s < 32 ? J : I, own_lo, own_hi, si.L, Wb) : -1;
         if (EMIT && cell >= 0) cell = row_ptr[g - own_lo] + cnt[cell];
         sbase[s] = cell;
         ssgn[s] = g < n_snp && flip != nullptr && flip[g] && !(KC && replayed_snp(counts, flip, sflags, g)) ? -1.0 : 1.0;
     }
-    f32x16v g8[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) g8[t] = f32x16v{};
-    const float* src = gram + (size_t)blockIdx.x * P * 8192 + lane * 16;
-    for (int p = 0; p < P; ++p)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const float4* q = reinterpret_cast<const float4*>(src + (size_t)p * 8192 + t * 1024);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float4 v = q[k];
-                g8[t][4 * k] += v.x; g8[t][4 * k + 1] += v.y; g8[t][4 * k + 2] += v.z; g8[t][4 * k + 3] += v.w;
-            }
-        }
-    __syncthreads();
-    if (diag) {  // m.x(a, b) = x.m(b, a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = g8[1][r];
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) g8[2][r] = tr[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
-    }
-    // ---- the plain epilogue (pair_epilogue, MB basis), each pair's correlations kept ----
+    __syncthreads();  // (sbase and ssgn are read by other lanes)
+    // ---- the plain epilogue, each pair's correlations kept ----
     const SnpSlot* info = sh.info;
-    const f32x16v &gxx = g8[0], &gxo = g8[1], &gox = g8[2], &goo = g8[3], &gxh = g8[4], &goh = g8[5], &ghx = g8[6],
-                  &gho = g8[7];
-    const double kslots = n_org;
     const R2Adj r2adj(n_org);
     const double qnan = __builtin_nan("");
     const int sj = 32 + i;
     const SnpSlot cj = info[sj];
-    const double sgj = ssgn[sj];
-    // the lane's 16 pairs: r, rd of the row SNP's entry (A_i . R_j) and of the column SNP's (R_i . A_j), and which of
-    // the 16 the row SNP (bit r of m_row: nij) and the column SNP (m_col: nji) need
-    double va[16], vd_row[16], vd_col[16];
-    unsigned m_row = 0, m_col = 0;
-    {
-        const SnpConst kj = sh.cst[sj];
-        const bool rpj = (cj.fl & 2) != 0;
-        SlotSum col = {0.0, 0.0, 0}, mine = {0.0, 0.0, 0};
-        int my_row = -1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {  // row group q: registers r = 4q + k, rows k + 8q + 4h
-            SlotSum rowv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = 4 * q + k;
-                const int si = k + 8 * q + 4 * h;
-                const SnpSlot ci = info[si];
-                const bool rpi = (ci.fl & 2) != 0;
-                const PairNeed need = pair_need(ci, cj, diag, ld_wind);
-                const bool nij = need.nij, nji = need.nji;
-                // (a diagonal item's entry above the diagonal also serves the one below it)
-                const bool nrev = diag && si < i && pair_need(cj, ci, true, ld_wind).nij;
-                SlotSum rv = {0.0, 0.0, 0};
-                va[r] = 0.0;
-                vd_row[r] = vd_col[r] = qnan;
-                if (nij || nji || nrev) {
-                    const SnpConst ki = sh.cst[si];
-                    const double mm = (double)goo[r];
-                    const double xx = 0.25 * ((double)gxx[r] - (double)gxo[r] - (double)gox[r] + mm);
-                    const double xo = ki.X - 0.5 * ((double)gxo[r] - mm);
-                    const double ox = kj.X - 0.5 * ((double)gox[r] - mm);
-                    const double oo = ki.Ob + kj.Ob - kslots + mm;
-                    const double aa = (xx - kj.mu * xo - ki.mu * (ox - kj.mu * oo)) * (ki.isa * kj.isa) +
-                                      (KC ? kj.ka * ki.SA + ki.ka * (kj.SA + kj.ka * n_org) : 0.0);
-                    const double r2 = r2adj(aa);
-                    const double sgi = ssgn[si];
-                    va[r] = aa * r2adj.inv_n * (sgi * sgj);
-                    if (nij) { rv.l2 = r2; rv.cnt = 1; m_row |= 1u << r; }
-                    if (nji) { col.l2 += r2; col.cnt += 1; m_col |= 1u << r; }
-                    if (DOM) {
-                        if (nij && rpj) {  // A_i . R_j -> L2D_i
-                            const double xh = 0.5 * ((double)gxh[r] - (double)goh[r]);
-                            const double oh = kj.H - (double)goh[r];
-                            const double ar = (2.0 * xh - kj.beta * xx - kj.c * xo -
-                                               ki.mu * (2.0 * oh - kj.beta * ox - kj.c * oo)) * (ki.isa * kj.is) +
-                                              (KC ? kj.kr * ki.SA + ki.ka * (kj.SR + kj.kr * n_org) : 0.0);
-                            const double rd = r2adj(ar);
-                            rv.l2d = rd;
-                            rv.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
-                            vd_row[r] = ar * r2adj.inv_n * sgi;
-                        }
-                        if (!diag && nji && rpi) {  // R_i . A_j -> L2D_j
-                            const double hx = 0.5 * ((double)ghx[r] - (double)gho[r]);
-                            const double ho = ki.H - (double)gho[r];
-                            const double ra = (2.0 * hx - ki.beta * xx - ki.c * ox -
-                                               kj.mu * (2.0 * ho - ki.beta * xo - ki.c * oo)) * (ki.is * kj.isa) +
-                                              (KC ? ki.kr * kj.SA + kj.ka * (ki.SR + ki.kr * n_org) : 0.0);
-                            const double rd = r2adj(ra);
-                            col.l2d += rd;
-                            col.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
-                            vd_col[r] = ra * r2adj.inv_n * sgj;
-                        }
-                    }
-                }
-                rowv[k] = rv;
-            }
-            if (!EMIT) {
-                const SlotSum t = reduce_rows4(rowv, i);  // lanes i >> 3 == k: row k + 8q + 4h
-                if ((i & 7) == q) {
-                    mine = t;
-                    my_row = (i >> 3) + 8 * q + 4 * h;
-                }
-            }
-        }
-        if (!EMIT) {
-            col = col + xlane<32>(col);  // the partner lane (i, 1 - h) holds the other 16 rows of column i
-            if (my_row >= 0) flush_slot(info[my_row], mine, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
-            if (h == 0) flush_slot(cj, col, own_lo, own_hi, n_snp, l2_acc, l2d_acc, ws_acc);
-        }
-    }
+    PairsSink<EMIT> sink{ssgn, r2adj.inv_n, ssgn[sj]};
+    pair_epilogue<DOM, f32x16v, true, KC>(sh.info, sh.cst, 0, 32, diag, i, h, g8[0], g8[1], g8[2], g8[3], g8[4], g8[5],
+                                          g8[6], g8[7], ld_wind, n_org, rsq_thr, n_org, own_lo, own_hi, n_snp, l2_acc,
+                                          l2d_acc, ws_acc, sink);
+    double (&va)[16] = sink.va, (&vd_row)[16] = sink.vd_row, (&vd_col)[16] = sink.vd_col;
+    const unsigned m_row = sink.m_row, m_col = sink.m_col;
     if (diag) {  // r(a, b) for a > b from the entry (b, a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) trd[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = va[r];
@@ -3800,21 +3651,29 @@ hipError_t launch_band_f4_q(const BandArgs& a, const int4* items4, int n_items4,
     return hipGetLastError();
 }
 
-hipError_t launch_band_f4_split(const BandArgs& a, int P, const int4* items, int n_items, float* gram, int which,
-                                const uint8_t* blk_miss) {
-    if (n_items <= 0) return hipSuccess;
+// The K-split launchers' first half: whether band_f4_part_kernel can split `a`'s rows into P pieces (unsegmented rows,
+// a two-chunk stage per piece at least), and, with `run`, its launch: the Gram tiles of n_items * P units to `gram`.
+static hipError_t launch_f4_part(const BandArgs& a, int P, const int4* items, int n_items, float* gram,
+                                 const uint8_t* blk_miss, bool run = true) {
     if (a.n_it > F4_SEG_CHUNKS || P < 1 || 2 * P > a.n_it) return hipErrorInvalidValue;
+    if (!run) return hipSuccess;
     const dim3 grid_p((unsigned)n_items * (unsigned)P);
-    if (!(which & 1)) goto kc;  // the partial tiles of every item come from the main launch
     if (a.dom) hipLaunchKernelGGL((band_f4_part_kernel<true>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS,
                                   P, gram, blk_miss, a.route_shift);
     else hipLaunchKernelGGL((band_f4_part_kernel<false>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS, P,
                             gram, blk_miss, a.route_shift);
+    return hipSuccess;
+}
+
+hipError_t launch_band_f4_split(const BandArgs& a, int P, const int4* items, int n_items, float* gram, int which,
+                                const uint8_t* blk_miss) {
+    if (n_items <= 0) return hipSuccess;
+    // (bit 0 of `which` clear: the partial tiles of every item come from the main launch)
+    if (launch_f4_part(a, P, items, n_items, gram, blk_miss, which & 1) != hipSuccess) return hipErrorInvalidValue;
 #define NLDSC_EPI(DOM_, KC_)                                                                                        \
     hipLaunchKernelGGL((band_f4_epi_kernel<DOM_, KC_>), dim3(n_items), dim3(64), 0, a.st, a.cst, items, A_SNPS,     \
                        A_EPI, a.blk_rep, P, gram, blk_miss, a.route_shift, nullptr)
-    if (a.dom) NLDSC_EPI(true, false); else NLDSC_EPI(false, false);
-kc:
+    if (which & 1) { if (a.dom) NLDSC_EPI(true, false); else NLDSC_EPI(false, false); }
     if (a.blk_rep && (which & 2)) { if (a.dom) NLDSC_EPI(true, true); else NLDSC_EPI(false, true); }
 #undef NLDSC_EPI
     return hipGetLastError();
@@ -3823,12 +3682,8 @@ kc:
 hipError_t launch_band_f4_annot(const BandArgs& a, const AnnotArgs& an, int P, const int4* items, int n_items,
                                 float* gram) {
     if (n_items <= 0) return hipSuccess;
-    if (a.n_it > F4_SEG_CHUNKS || P < 1 || 2 * P > a.n_it || an.n_annot < 1) return hipErrorInvalidValue;
-    const dim3 grid_p((unsigned)n_items * (unsigned)P);
-    if (a.dom) hipLaunchKernelGGL((band_f4_part_kernel<true>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS,
-                                  P, gram, nullptr, a.route_shift);
-    else hipLaunchKernelGGL((band_f4_part_kernel<false>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS, P,
-                            gram, nullptr, a.route_shift);
+    if (an.n_annot < 1) return hipErrorInvalidValue;
+    if (launch_f4_part(a, P, items, n_items, gram, nullptr) != hipSuccess) return hipErrorInvalidValue;
 #define NLDSC_EPI(DOM_, KC_)                                                                                        \
     hipLaunchKernelGGL((band_f4_epi_annot_kernel<DOM_, KC_>), dim3(n_items), dim3(64), 0, a.st, a.cst, items,      \
                        A_SNPS, A_EPI, a.blk_rep, P, gram, an.annot, an.ascale, an.n_annot, an.l2c_acc, an.l2dc_acc,   \
@@ -3842,15 +3697,9 @@ hipError_t launch_band_f4_annot(const BandArgs& a, const AnnotArgs& an, int P, c
 hipError_t launch_band_f4_pairs(const BandArgs& a, const PairsArgs& pa, int P, const int4* items, int n_items,
                                 float* gram, bool emit, bool run_part) {
     if (n_items <= 0) return hipSuccess;
-    if (a.n_it > F4_SEG_CHUNKS || P < 1 || 2 * P > a.n_it || pa.cnt == nullptr || pa.Wb < 1) return hipErrorInvalidValue;
+    if (pa.cnt == nullptr || pa.Wb < 1) return hipErrorInvalidValue;
     if (emit && (!pa.row_ptr || !pa.k || !pa.r || !pa.rd)) return hipErrorInvalidValue;
-    const dim3 grid_p((unsigned)n_items * (unsigned)P);
-    if (run_part) {
-        if (a.dom) hipLaunchKernelGGL((band_f4_part_kernel<true>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items,
-                                      A_SNPS, P, gram, nullptr, a.route_shift);
-        else hipLaunchKernelGGL((band_f4_part_kernel<false>), grid_p, dim3(64), 0, a.st, A_ROWS, a.cst, items, A_SNPS,
-                                P, gram, nullptr, a.route_shift);
-    }
+    if (launch_f4_part(a, P, items, n_items, gram, nullptr, run_part) != hipSuccess) return hipErrorInvalidValue;
 #define NLDSC_EPI(DOM_, KC_, EMIT_)                                                                                  \
     hipLaunchKernelGGL((band_f4_epi_pairs_kernel<DOM_, KC_, EMIT_>), dim3(n_items), dim3(64), 0, a.st, a.cst, items, \
                        A_SNPS, A_EPI, a.blk_rep, P, gram, pa.cnt, pa.Wb, pa.row_ptr, pa.n_pairs, pa.k, pa.r, pa.rd,   \
