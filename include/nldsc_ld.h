@@ -117,6 +117,7 @@ void nldsc_engine_destroy(nldsc_engine* e);
  *   annot_batch_items [0] annotated runs: block-pair items per batch (0: what the Gram scratch cap holds)
  *   pairs_batch_items [0] pairs runs: the same
  *   pairs_max_cells   [0] pairs runs: cells of the dense count matrix a run may use (0: 2^27)
+ *   cov_batch_items   [0] covariate runs: block-pair items per batch (0: what the Gram scratch cap holds)
  *   debug_timing [0] per-run stage timings on stderr */
 int nldsc_engine_set_option(nldsc_engine* e, const char* name, int64_t value, char* err, size_t errlen);
 
@@ -221,6 +222,45 @@ int nldsc_engine_run_annot(nldsc_engine* e, const nldsc_ld_params* p, const doub
 int nldsc_engine_run_pairs(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,
                            nldsc_ld_result* r, double min_r2, int64_t* row_ptr, int32_t* k, double* rv,
                            double* rdv, int64_t cap, int64_t* n_pairs, char* err, size_t errlen);
+
+/* Covariate-adjusted LD scores (cov-LDSC, Luo et al., Hum. Mol. Genet. 2021, here also for the dominance scores):
+ * nldsc_engine_run with every genotype vector residualised on the run's covariates before the correlations, for LD
+ * scores that match summary statistics computed with those covariates (principal components, sex, age) in the model.
+ * q_basis is category-major [n_covar][p->n_org] host memory: an orthonormal basis Q of the centred covariates' column
+ * space (the caller drops constant and dependent columns; the engine takes Q, not the covariates), row i = .fam line
+ * i of the image's individuals (the kept ones, in order, for an image loaded with a keep list).
+ *   - With A_j, R_j SNP j's standardised additive and dominance-residual vectors (0 at missing calls), U_j = Q^T A_j,
+ *     W_j = Q^T R_j, v_j = 1 - |U_j|^2 / N:  A~_j = (A_j - Q U_j) / sqrt(v_j);  R~_j = the standardised residual of
+ *     the dominance coding on the intercept, A_j and the covariates: (R_j - Q W_j - g_j (A_j - Q U_j)) / sqrt(w_j),
+ *     g_j = -(W_j . U_j) / (N v_j), w_j = 1 - |W_j|^2 / N - g_j^2 v_j.  L2[j] = 1 + sum_k r2adj(A~_j . A~_k / N),
+ *     L2D[j] = sum_k r2adj(A~_j . R~_k / N) over the neighbour sets of the plain run, r2adj(r) = 1 - (1 - r^2)
+ *     (n' - 1) / (n' - 2) with n' = N - n_covar.
+ *   - maf, l2_ws and the windows are the plain run's, bit for bit.  residuals_std[j] is rstd_j sqrt(w_j), the std of
+ *     the residual of the model with covariates; l2d_ws / l2d_wse membership (std > std_thr) is taken on it.
+ *   - v_j < 1e-6 (the additive coding is, to rounding, a linear function of the covariates): A~_j := 0, every r with
+ *     it is 0, the SNP stays computed.  w_j < 1e-6: R~_j := 0 and residual std 0.  NaN patterns are the plain run's.
+ *   - The run implies NLDSC_FLAG_EXACT_RARE (closed-form vectors of rare variants: the reference has no such model
+ *     whose fp32 rounding could be replayed).  Results do not depend on the schedule (engine options, batches,
+ *     K-split, owned ranges) and are bit-reproducible.
+ *   - NLDSC_E_ARG, with the reason in `err`, unless 1 <= n_covar <= NLDSC_MAX_COVAR and n_covar <= n_org - 3; every
+ *     value of q_basis is finite, its Gram matrix is within 1e-8 of the identity and its column sums within
+ *     1e-8 sqrt(n_org) of 0; the run takes the exact fp4 path with n_org < 2^19 (as an annotated run) in PLINK's sample
+ *     order (NLDSC_FLAG_STRICT_PLINK_ORDER, or an image of kept samples).  Host results only: the device-table and split
+ *     runs take no covariates, and covariates with annotations or a pair table in one run are not supported.
+ *   - The projections go first (one pass over the resident image on the fp64 matrix cores, part of the statistics
+ *     stage's time), then the band in batches like an annotated run's (option cov_batch_items).  Stateless: the next
+ *     run is a plain one. */
+#define NLDSC_MAX_COVAR 64
+int nldsc_engine_run_covar(nldsc_engine* e, const nldsc_ld_params* p, const double* q_basis, int32_t n_covar,
+                           int32_t own_begin, int32_t own_end, nldsc_ld_result* r, char* err, size_t errlen);
+/* One-shot: read `p->bedfile`, on the individuals keep_idx[n_keep] when keep_idx != NULL (nldsc_ld_calculate_keep;
+ * q_basis then has n_keep rows), in PLINK's sample order. */
+int nldsc_ld_calculate_covar(const nldsc_ld_params* p, const int32_t* keep_idx, int32_t n_keep, const double* q_basis,
+                             int32_t n_covar, nldsc_ld_result* r, char* err, size_t errlen);
+/* The projections of the last covariate run, for tests and tools: u, w [n_covar][n_snp] (U_j in the file's allele
+ * coding, W_j), v, wd [n_snp] (v_j, w_j; 1 for SNPs that are not computed or have every call missing, whose U and W
+ * are 0).  Any pointer may be NULL.  NLDSC_E_ARG when the engine's last covariate run did not complete. */
+int nldsc_engine_covar_projections(nldsc_engine* e, double* u, double* w, double* v, double* wd);
 
 /* nldsc_engine_run with the owned slice of the result left in device memory (the multi-GPU gather of
  * SURVEY.md §8 e1 then runs device to device over RCCL, without a host round trip): `table_dev`, device memory

@@ -36,8 +36,10 @@ EXPORTED = (
     "nldsc_engine_result_direct", "nldsc_engine_set_keep", "nldsc_engine_kept", "nldsc_ld_calculate_keep",
     "nldsc_engine_run_annot", "nldsc_ld_calculate_annot", "nldsc_annot_scale_exp", "nldsc_annot_plan_batches",
     "nldsc_engine_run_pairs", "nldsc_pairs_cell", "nldsc_pairs_window_blocks", "nldsc_pairs_split_ranges",
+    "nldsc_engine_run_covar", "nldsc_ld_calculate_covar", "nldsc_engine_covar_projections",
 )
 MAX_ANNOT = 1024  # NLDSC_MAX_ANNOT
+MAX_COVAR = 64  # NLDSC_MAX_COVAR
 
 
 class Params(ctypes.Structure):
@@ -148,6 +150,12 @@ def lib(path: str | None = None) -> ctypes.CDLL:
             L.nldsc_pairs_cell.argtypes = [ctypes.c_int32] * 6
             L.nldsc_pairs_window_blocks.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
             L.nldsc_pairs_split_ranges.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, vp, ctypes.c_int32]
+        if hasattr(L, "nldsc_engine_run_covar"):
+            L.nldsc_engine_run_covar.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.POINTER(Result)] + c_err
+            L.nldsc_ld_calculate_covar.argtypes = [ctypes.POINTER(Params), vp, ctypes.c_int32, vp, ctypes.c_int32,
+                                                   ctypes.POINTER(Result)] + c_err
+            L.nldsc_engine_covar_projections.argtypes = [vp, vp, vp, vp, vp]
         L.nldsc_synth_bed_device.argtypes = [ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float,
                                              ctypes.c_uint64] + c_err
@@ -260,6 +268,17 @@ def annot_matrix(annot, n_snp: int) -> np.ndarray:
         a = a[:, None]
     if a.ndim != 2 or a.shape[0] != n_snp:
         raise ValueError(f"annot must have shape (n_snp={n_snp}, C), got {a.shape}")
+    return np.ascontiguousarray(a.T)
+
+
+def covar_basis_matrix(q, n_org: int) -> np.ndarray:
+    """An [n_org, q] orthonormal covariate basis (a 1-D array is one column) as the C ABI's category-major
+    [q][n_org] float64 array (nldsc_engine_run_covar q_basis)."""
+    a = np.asarray(q, dtype=np.float64)
+    if a.ndim == 1:
+        a = a[:, None]
+    if a.ndim != 2 or a.shape[0] != n_org:
+        raise ValueError(f"covar must have shape (n_org={n_org}, q), got {a.shape}")
     return np.ascontiguousarray(a.T)
 
 

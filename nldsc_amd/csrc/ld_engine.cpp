@@ -324,6 +324,14 @@ struct nldsc_engine {
     std::vector<int> h_pairs_len;
     int pairs_batch_items = 0;
     int64_t pairs_max_cells = 0;
+    // covariate runs (nldsc_engine_run_covar): the basis as the projection kernel reads it (ld_kernels.h CovArgs qt,
+    // built in h_qt), the projection's plane sums, then U | W | W' ([3][n_covar][M]) and isv, gamma, isw, v, w
+    // ([5][M]); option "cov_batch_items" (as annot_batch_items); cov_n / cov_M: the covariates and SNPs of the last
+    // covariate run (nldsc_engine_covar_projections; 0: none yet)
+    DevBuf<double> cov_qt, cov_part, cov_uw, cov_sc;
+    std::vector<double> h_qt;
+    int cov_batch_items = 0;
+    int cov_n = 0, cov_M = 0;
     // the device table of a run (finish_table's input), kept for a split run between its two calls
     // (nldsc_engine_run_device_split / _finish: `pending`)
     struct SplitState {
@@ -607,6 +615,7 @@ int nldsc_engine_set_option(nldsc_engine* e, const char* name, int64_t value, ch
         {"annot_batch_items", 0, INT32_MAX, [&](int64_t v) { e->annot_batch_items = (int)v; }},
         {"pairs_batch_items", 0, INT32_MAX, [&](int64_t v) { e->pairs_batch_items = (int)v; }},
         {"pairs_max_cells", 0, INT64_MAX, [&](int64_t v) { e->pairs_max_cells = v; }},
+        {"cov_batch_items", 0, INT32_MAX, [&](int64_t v) { e->cov_batch_items = (int)v; }},
         {"debug_timing", 0, 1, [&](int64_t v) { e->debug_timing = v != 0; }},
     };
     for (const Opt& o : opts)
@@ -1054,6 +1063,94 @@ int resolve_host_out(nldsc_engine* e, const nldsc_ld_result* r, int own_begin, i
     return NLDSC_OK;
 }
 
+// A covariate run's request (nldsc_engine_run_covar): the caller's orthonormal basis, [n][n_org]
+struct CovRun {
+    const double* q;
+    int n;
+};
+
+nldsc::CovArgs cov_args(const nldsc_engine* e, const RunShape& s, const CovRun& cv) {
+    const size_t qm = (size_t)cv.n * (size_t)s.M;
+    return {e->cov_qt.p, cv.n, e->cov_part.p, e->cov_uw.p, e->cov_uw.p + qm, e->cov_uw.p + 2 * qm, e->cov_sc.p};
+}
+
+// The restrictions of a covariate run, each with its reason (those of an annotated run: the same partial kernel; and
+// the sample order the basis rows are in), the basis checked (finite, orthonormal, centred) and uploaded in the
+// projection kernel's tile order (on the main stream, before the prologue), the buffers sized.
+int prepare_cov(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const CovRun& cv, bool other, char* err,
+                size_t errlen) {
+    if (other)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "covariates with annotations or a pair table in one run are not supported");
+    if (cv.n < 1 || cv.n > NLDSC_MAX_COVAR)
+        return set_err(err, errlen, NLDSC_E_ARG, "n_covar %d outside [1, %d]", cv.n, NLDSC_MAX_COVAR);
+    if (!cv.q) return set_err(err, errlen, NLDSC_E_ARG, "q_basis is NULL");
+    if (cv.n > p->n_org - 3)
+        return set_err(err, errlen, NLDSC_E_ARG, "n_covar %d leaves fewer than 3 degrees of freedom of %d individuals",
+                       cv.n, p->n_org);
+    if (p->n_org >= (1 << 19))
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "covariate runs need n_org < 2^19 (got %d): the K-split partial kernel takes unsegmented rows",
+                       p->n_org);
+    if (s.path != 2)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "covariate runs take the exact fp4 path only: this run's flags or the band_mode option select %s",
+                       s.path == 0 ? "fp32" : "exact int8");
+    if (!s.strict)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "covariate runs use PLINK's sample order (the basis rows are .fam lines): set "
+                       "NLDSC_FLAG_STRICT_PLINK_ORDER");
+    const size_t N = (size_t)s.N, C = (size_t)cv.n;
+    const double tol_sum = 1e-8 * std::sqrt((double)s.N);
+    for (size_t c = 0; c < C; ++c) {
+        const double* col = cv.q + c * N;
+        double sum = 0.0;
+        for (size_t i = 0; i < N; ++i) {
+            if (!std::isfinite(col[i]))
+                return set_err(err, errlen, NLDSC_E_ARG, "q_basis column %zu, individual %zu: the value is not finite",
+                               c, i);
+            sum += col[i];
+        }
+        if (!(std::fabs(sum) <= tol_sum))
+            return set_err(err, errlen, NLDSC_E_ARG,
+                           "q_basis column %zu is not centred: its sum is %.3e (limit 1e-8 sqrt(n_org))", c, sum);
+    }
+    for (size_t a = 0; a < C; ++a)
+        for (size_t b = a; b < C; ++b) {
+            const double *x = cv.q + a * N, *y = cv.q + b * N;
+            double d[4] = {0.0, 0.0, 0.0, 0.0};
+            size_t i = 0;
+            for (; i + 4 <= N; i += 4)
+                for (int k = 0; k < 4; ++k) d[k] += x[i + k] * y[i + k];
+            for (; i < N; ++i) d[0] += x[i] * y[i];
+            const double dot = (d[0] + d[1]) + (d[2] + d[3]);
+            if (!(std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-8))
+                return set_err(err, errlen, NLDSC_E_ARG,
+                               "q_basis is not orthonormal: columns %zu . %zu = %.12g (limit 1e-8 from %d)", a, b, dot,
+                               a == b ? 1 : 0);
+        }
+    // the projection kernel's tiles: [chunk][group][128 samples][16 covariates], zero padded
+    const int NG = nldsc::covar_groups(cv.n);
+    const size_t tile = (size_t)128 * 16 * NG, n_qt = (size_t)s.n_it * tile;
+    e->h_qt.assign(n_qt, 0.0);
+    for (size_t c = 0; c < C; ++c) {
+        const double* col = cv.q + c * N;
+        const size_t g = c / 16, cc = c % 16;
+        for (size_t i = 0; i < N; ++i) e->h_qt[(i / 128) * tile + (g * 128 + i % 128) * 16 + cc] = col[i];
+    }
+    HIPCHK(hipSetDevice(e->device));
+    const size_t M = (size_t)s.M;
+    const int P = nldsc::covar_pieces(s.nblk, s.n_it, e->n_cu);
+    HIPCHK(e->cov_qt.ensure(n_qt));
+    HIPCHK(e->cov_part.ensure((size_t)P * (size_t)s.nblk * 96 * 16 * NG));
+    HIPCHK(e->cov_uw.ensure(3 * C * M));
+    HIPCHK(e->cov_sc.ensure(5 * M));
+    e->cov_n = e->cov_M = 0;  // (no projections to report until this run's are written)
+    HIPCHK(hipMemcpyAsync(e->cov_qt.p, e->h_qt.data(), sizeof(double) * n_qt, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return NLDSC_OK;
+}
+
 // the work buffers of a run, sized (allocation happens on the first run of a size; the enqueue phases allocate only
 // what depends on the schedule's counts)
 int ensure_run_buffers(nldsc_engine* e, const RunShape& s, const PlanMode& m, char* err, size_t errlen) {
@@ -1100,7 +1197,7 @@ int ensure_run_buffers(nldsc_engine* e, const RunShape& s, const PlanMode& m, ch
 // plan on the plan stream beside them, then statistics, pair range, replay flags, left pointers, the blocks' missing
 // flags, and the rare-variant replay on the side stream.
 int enqueue_prologue(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m, char* err,
-                     size_t errlen) {
+                     size_t errlen, const CovRun* cv = nullptr) {
     const int M = s.M;
     hipStream_t st = e->stream, cs = e->copy_stream, ps = e->plan_stream;
     const uint8_t* flip = e->oriented ? e->flip.p : nullptr;
@@ -1142,6 +1239,12 @@ int enqueue_prologue(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& 
                                    e->l2d_acc.p, e->ws_acc.p, e->blk_rep.p));
     // split runs: the pairs whose lower SNP is owned (flag bit 3), before the replay may touch the flags (ev_stats)
     if (s.split) HIPCHK(nldsc::launch_pair_range(e->sflags.p, M, s.own_begin, s.own_end, st));
+    // covariate runs: every SNP's projections on the covariate basis, then its residual std and residual-pass flag
+    // (bit 1) for the model with covariates — before anything reads that bit (the band); part of the statistics
+    // stage's time (ev[1] .. ev[2])
+    if (cv)
+        HIPCHK(nldsc::launch_covar_project(e->bed.p, s.row_bytes, M, s.N, e->counts.p, p->std_thr, cov_args(e, s, *cv),
+                                           nldsc::covar_pieces(s.nblk, s.n_it, e->n_cu), e->sflags.p, e->rstd.p, st));
     // rare variants: the reference's fp32 residual replayed (its sums assume N < 2^23); the flags per block here,
     // the replay itself after the schedule (below)
     // Invariant of the overlap: the replay rewrites, for replayed SNPs only, sflags bit 1 (residual pass; a byte
@@ -1430,6 +1533,46 @@ int enqueue_band_annot(nldsc_engine* e, const nldsc_ld_params* p, const RunShape
     return NLDSC_OK;
 }
 
+// The band of a covariate run (ev[3] .. ev[4]): the single-block items in batches (as an annotated band's) through the
+// K-split partial kernel and the covariate epilogue (launch_band_f4_cov); no replay to wait for (prepare_cov's run
+// takes the closed-form vectors); then the issued-product count as enqueue_band queues it.
+int enqueue_band_cov(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m,
+                     const Schedule& sc, const CovRun& cv, char* err, size_t errlen) {
+    hipStream_t st = e->stream, cs = e->copy_stream;
+    const int n_items = sc.n_items;
+    HIPCHK(hipEventRecord(e->ev[3], st));
+    const std::vector<nldsc::AnnotBatch> batches = nldsc::plan_annot_batches(
+        n_items, s.n_it, e->n_cu, e->ksplit_ok, e->cov_batch_items, nldsc::ANNOT_GRAM_CAP_BYTES);
+    size_t units = 0;
+    int p_max = 1;
+    for (const nldsc::AnnotBatch& b : batches) {
+        units = std::max(units, (size_t)b.n * (size_t)b.ksplit);
+        p_max = std::max(p_max, b.ksplit);
+    }
+    e->n_band_items = n_items;
+    e->last_ksplit = p_max;
+    e->last_round_items = 0;
+    e->last_tail_ksplit = 1;
+    e->last_band_kernel = NLDSC_BAND_F4_KSPLIT;
+    HIPCHK(e->gram.ensure(std::max<size_t>(units, 1) * 8192));
+    const nldsc::BandArgs a = fill_band_args(e, p, s, m);
+    const nldsc::CovArgs ca = cov_args(e, s, cv);
+    for (const nldsc::AnnotBatch& b : batches)
+        HIPCHK(nldsc::launch_band_f4_cov(a, ca, b.ksplit, e->items.p + b.first, b.n, e->gram.p));
+    e->last_path = s.path;
+    HIPCHK(hipEventRecord(e->ev[4], st));
+    HIPCHK(e->sums.ensure(3));
+    HIPCHK(e->h_sums.ensure(3 * sizeof(unsigned long long)));
+    HIPCHK(hipStreamWaitEvent(cs, e->ev[3], 0));
+    HIPCHK(hipMemsetAsync(e->sums.p + 2, 0, sizeof(unsigned long long), cs));
+    HIPCHK(nldsc::launch_issued_products(e->items.p, n_items, nullptr, 0, m.gpu_plan ? e->plan_rows.p : nullptr,
+                                         e->blk_miss.p, s.nblk, s.path, s.dom, 0, m.route_shift, e->sums.p + 2, cs));
+    HIPCHK(hipMemcpyAsync(e->h_sums.p + 2 * sizeof(unsigned long long), e->sums.p + 2, sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipEventRecord(e->ev_issued, cs));
+    return NLDSC_OK;
+}
+
 // A pairs run's request (nldsc_engine_run_pairs): the filter, the caller's CSR arrays and their capacity; `emitted`:
 // the table is in the device buffers, to be copied out once the stream is drained
 struct PairsRun {
@@ -1547,7 +1690,9 @@ int enqueue_band_pairs(nldsc_engine* e, const nldsc_ld_params* p, const RunShape
 // single-block launches, the KC launches after the replay (ev_replay), or the fp32 launch; then the issued-product
 // count on the side stream (ev_issued).
 int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m, const Schedule& sc,
-                 char* err, size_t errlen, const AnnotRun* an = nullptr, PairsRun* pr = nullptr) {
+                 char* err, size_t errlen, const AnnotRun* an = nullptr, PairsRun* pr = nullptr,
+                 const CovRun* cv = nullptr) {
+    if (cv) return enqueue_band_cov(e, p, s, m, sc, *cv, err, errlen);
     if (an) return enqueue_band_annot(e, p, s, m, sc, *an, err, errlen);
     if (pr) return enqueue_band_pairs(e, p, s, m, sc, *pr, err, errlen);
     hipStream_t st = e->stream, cs = e->copy_stream;
@@ -1710,10 +1855,13 @@ int finish_host(nldsc_engine* e, const RunShape& s, const HostOut& o, double* sw
 int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end, nldsc_ld_result* r,
              double* table_dev, int32_t width, char* err, size_t errlen, long long* export_dev = nullptr,
              int32_t export_cap = 0, int32_t* export_n = nullptr, const AnnotRun* an = nullptr,
-             PairsRun* pr = nullptr) {
+             PairsRun* pr = nullptr, const CovRun* cv = nullptr) {
     const bool split = export_n != nullptr;
     int rc = check_run_args(e, p, own_begin, own_end, r, table_dev, width, split, export_dev, export_cap, err, errlen);
     if (rc) return rc;
+    if (cv && (rc = prepare_cov(e, p, run_shape(e, p, own_begin, own_end, split), *cv, an != nullptr || pr != nullptr,
+                                err, errlen)))
+        return rc;
     if (an && (rc = prepare_annot(e, p, run_shape(e, p, own_begin, own_end, split), *an, err, errlen))) return rc;
     if (pr && (rc = prepare_pairs(p, run_shape(e, p, own_begin, own_end, split), *pr, an != nullptr, err, errlen)))
         return rc;
@@ -1724,11 +1872,11 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     e->last_direct = -1;
     if (!table_dev && (rc = resolve_host_out(e, r, own_begin, own_end, &out, err, errlen))) return rc;
     const RunShape s = run_shape(e, p, own_begin, own_end, split);
-    const PlanMode m = plan_mode(e, p, s, an != nullptr || pr != nullptr);
+    const PlanMode m = plan_mode(e, p, s, an != nullptr || pr != nullptr || cv != nullptr);
     if ((rc = ensure_run_buffers(e, s, m, err, errlen))) return rc;
 
     const auto t_start = Clock::now();
-    if ((rc = enqueue_prologue(e, p, s, m, err, errlen))) return rc;
+    if ((rc = enqueue_prologue(e, p, s, m, err, errlen, cv))) return rc;
     // ---- window replay + schedule ----
     const auto t_host0 = Clock::now();
     Schedule sc;
@@ -1736,7 +1884,7 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     if (rc) return rc;
     // (l2_acc, l2d_acc and ws_acc were zeroed by snp_stats_kernel)
     const auto t_host1 = Clock::now();
-    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen, an, pr))) return rc;
+    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen, an, pr, cv))) return rc;
     if (an) {  // the per-annotation scores of the owned slice, finalized beside the ordinary ones (.. ev[5])
         double* o2 = e->annot_out.p;
         HIPCHK(nldsc::launch_finalize_annot(e->Lw.p, e->ws_acc.p, annot_args(e, s, *an), s.M, own_begin, own_end, s.dom,
@@ -1793,6 +1941,7 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
                      e->ms[5], e->ms[2]);
     }
     record_metrics(e, sw, sd, s.N, s.row_bytes);
+    if (cv) e->cov_n = cv->n, e->cov_M = s.M;  // (the projections of this run are on the device)
     return NLDSC_OK;
 }
 
@@ -1825,6 +1974,35 @@ int nldsc_engine_run_pairs(nldsc_engine* e, const nldsc_ld_params* p, int32_t ow
         return set_err(err, errlen, NLDSC_E_SPACE, "the pair table needs room for %lld pairs (capacity %lld)",
                        (long long)*n_pairs, (long long)(k ? cap : 0));
     return NLDSC_OK;
+}
+
+int nldsc_engine_run_covar(nldsc_engine* e, const nldsc_ld_params* p, const double* q_basis, int32_t n_covar,
+                           int32_t own_begin, int32_t own_end, nldsc_ld_result* r, char* err, size_t errlen) {
+    if (!r || !p) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
+    // the closed-form vectors of rare variants: the reference's fp32 rounding is not replayed for a model it lacks
+    nldsc_ld_params q = *p;
+    q.flags |= NLDSC_FLAG_EXACT_RARE;
+    const CovRun cv = {q_basis, n_covar};
+    return run_impl(e, &q, own_begin, own_end, r, nullptr, 0, err, errlen, nullptr, 0, nullptr, nullptr, nullptr, &cv);
+}
+
+int nldsc_engine_covar_projections(nldsc_engine* e, double* u, double* w, double* v, double* wd) {
+    if (!e || e->cov_n == 0) return NLDSC_E_ARG;
+    if (hipSetDevice(e->device) != hipSuccess) return NLDSC_E_HIP;
+    const size_t M = (size_t)e->cov_M, qm = (size_t)e->cov_n * M;
+    hipError_t he = hipSuccess;
+    if (u) he = hipMemcpy(u, e->cov_uw.p, sizeof(double) * qm, hipMemcpyDeviceToHost);
+    if (he == hipSuccess && w) he = hipMemcpy(w, e->cov_uw.p + qm, sizeof(double) * qm, hipMemcpyDeviceToHost);
+    if (he == hipSuccess && v) he = hipMemcpy(v, e->cov_sc.p + 3 * M, sizeof(double) * M, hipMemcpyDeviceToHost);
+    if (he == hipSuccess && wd) he = hipMemcpy(wd, e->cov_sc.p + 4 * M, sizeof(double) * M, hipMemcpyDeviceToHost);
+    if (he == hipSuccess && u && e->oriented) {  // the file's allele coding: a row stored flipped has U negated
+        std::vector<uint8_t> fl(M);
+        he = hipMemcpy(fl.data(), e->flip.p, M, hipMemcpyDeviceToHost);
+        for (size_t c = 0; he == hipSuccess && c < (size_t)e->cov_n; ++c)
+            for (size_t j = 0; j < M; ++j)
+                if (fl[j]) u[c * M + j] = -u[c * M + j];
+    }
+    return he == hipSuccess ? NLDSC_OK : NLDSC_E_HIP;
 }
 
 int nldsc_engine_run_device(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,
@@ -1932,6 +2110,24 @@ int nldsc_ld_calculate_annot(const nldsc_ld_params* p, const int32_t* keep_idx, 
         nldsc_ld_params q = *p;
         q.n_org = e->n_org;  // the kept count (p->n_org without a list)
         rc = nldsc_engine_run_annot(e, &q, annot, n_annot, 0, p->n_snp, r, l2_annot, l2d_annot, err, errlen);
+    }
+    nldsc_engine_destroy(e);
+    return rc;
+}
+
+int nldsc_ld_calculate_covar(const nldsc_ld_params* p, const int32_t* keep_idx, int32_t n_keep, const double* q_basis,
+                             int32_t n_covar, nldsc_ld_result* r, char* err, size_t errlen) {
+    if (!p || !r || !p->bedfile) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
+    nldsc_engine* e = nullptr;
+    int rc = nldsc_engine_create(p->device, &e, err, errlen);
+    if (rc) return rc;
+    if (keep_idx) rc = nldsc_engine_set_keep(e, keep_idx, n_keep, p->n_org, err, errlen);
+    if (!rc) rc = nldsc_engine_load_bed_file(e, p->bedfile, p->n_snp, p->n_org, err, errlen);
+    if (!rc) {
+        nldsc_ld_params q = *p;
+        q.n_org = e->n_org;  // the kept count (p->n_org without a list)
+        q.flags |= NLDSC_FLAG_STRICT_PLINK_ORDER;  // (q_basis rows are .fam lines)
+        rc = nldsc_engine_run_covar(e, &q, q_basis, n_covar, 0, p->n_snp, r, err, errlen);
     }
     nldsc_engine_destroy(e);
     return rc;

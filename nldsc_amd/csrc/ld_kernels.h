@@ -173,6 +173,28 @@ hipError_t launch_band_f4_annot(const BandArgs& a, const AnnotArgs& an, int P, c
 // device memory; out_l2d may be nullptr), NaN where the plain L2 / L2D are (and L2D everywhere without dom)
 hipError_t launch_finalize_annot(const int* Lw, const int* ws_acc, const AnnotArgs& an, int n_snp, int own_lo,
                                  int own_hi, bool dom, double* out_l2, double* out_l2d, hipStream_t st);
+// Covariate-adjusted LD scores (nldsc_engine_run_covar; ld_kernels.hip "covariate-adjusted LD scores").  qt: the
+// orthonormal covariate basis as the projection kernel reads it, n_it tiles of [covar_groups(n_covar)][128][16] fp64
+// (tile t, group g, slot s, column c = Q[128 t + s][16 g + c], 0 for samples >= n_org and covariates >= n_covar);
+// part: the projection's plane sums, P * nblk * 96 * 16 * groups doubles; u, w, wp: U, W, W' ([n_covar][n_snp]); sc:
+// [5][n_snp] isv, gamma, isw, v, w.
+struct CovArgs {
+    const double* qt;
+    int n_covar;
+    double *part, *u, *w, *wp, *sc;
+};
+int covar_groups(int n_covar);                      // 16-covariate groups of the projection kernel: 1 .. 4
+int covar_pieces(int nblk, int n_it, int n_cu);     // K pieces of the projection (<= n_it)
+// the projection (covar_project_kernel over nblk x P workgroups) and the per-SNP kernel after it, which also rewrites
+// rstd_out and sflags bit 1 (residual pass) for the covariate model; after launch_tail_counts (fp4 padding: the rows'
+// non-individual slots are 00) and launch_snp_stats (counts [4 j + k], the plain flags and residual std)
+hipError_t launch_covar_project(const uint8_t* img, int row_bytes, int n_snp, int n_org, const int* counts,
+                                double std_thr, const CovArgs& cv, int P, uint8_t* sflags, double* rstd_out,
+                                hipStream_t st);
+// one batch of a covariate band: band_f4_part_kernel as launch_band_f4_annot runs it, then band_f4_epi_cov_kernel
+// (a.blk_rep must be nullptr: no replay in a covariate run)
+hipError_t launch_band_f4_cov(const BandArgs& a, const CovArgs& cv, int P, const int4* items, int n_items,
+                              float* gram);
 // Pair tables (nldsc_engine_run_pairs): the dense count matrix cnt[own_n][Wb] (band_plan.h pairs_cell; zeroed before
 // the count pass, turned into each row's exclusive offsets by launch_pairs_row_scan), and for the emit pass the
 // table's row_ptr (own_n + 1, device memory), its n_pairs entries k / r / rd; min_r2: NaN = no filter; flip (or

@@ -1266,6 +1266,8 @@ __device__ __forceinline__ double r2_adjusted(double dot, double n) {
 struct R2Adj {
     double inv_n, q;
     __device__ __forceinline__ explicit R2Adj(double n) : inv_n(1. / n), q((n - 1) / (n - 2)) {}
+    // covariate runs: the correlation over the n individuals, the adjustment with n' = n - q degrees of freedom
+    __device__ __forceinline__ R2Adj(double n, double n_adj) : inv_n(1. / n), q((n_adj - 1) / (n_adj - 2)) {}
     __device__ __forceinline__ double operator()(double dot) const {
         const double corr = dot * inv_n;
         return 1. - (1. - corr * corr) * q;
@@ -1607,6 +1609,24 @@ struct NoSink {
     __device__ __forceinline__ constexpr void end(int) const {}
 };
 
+// The covariate mode of pair_epilogue (covariate-adjusted LD scores, band_f4_epi_cov_kernel).  With U_j = Q^T A_j,
+// W'_j = Q^T R_j - gamma_j U_j of the orthonormal covariate basis Q, the pair's adjusted dots follow from its plain
+// ones:  A~_i . A~_j = (aa - U_i . U_j) isv_i isv_j,  A~_i . R~_j = (ar - gamma_j aa - U_i . W'_j) isv_i isw_j  and
+// R~_i . A~_j likewise (isv = 1 / sqrt(v), isw = 1 / sqrt(w), 0 for a SNP the covariates explain: covar_finish_kernel).
+// NoCov (the default): off, nothing of it is compiled.  CovTiles: the q-length dot products of the lane's 16 pairs,
+// d[0] U_i . U_j, d[1] U_i . W'_j, d[2] W'_i . U_j ([..][r][lane], LDS), the per-slot isv / gam / isw of the item's
+// 64 slots (LDS) and n' = n_org - q of r2adj.
+struct NoCov {
+    static constexpr bool ON = false;
+};
+struct CovTiles {
+    static constexpr bool ON = true;
+    const double (*d)[16][64];
+    const double *isv, *gam, *isw;
+    double n_adj;
+    int lane;
+};
+
 // Epilogue of one 32x32 block pair (row slots rb.., column slots cb.. of the slot tables `info` / `cst`):
 // standardised dots from the 8 integer Gram entries in fp64, r2adj, window/pointer masks, and the pair's
 // per-SNP sums (ldscalc.h:33-55), reduced across the wave in registers (reduce_rows4) and added to the per-SNP
@@ -1615,16 +1635,23 @@ struct NoSink {
 // gho h.m, and `kslots` is the number of individual slots (n_org; the other slots are all-zero in every
 // plane); o = 1 - m over the individual slots.
 // sink: a consumer of the single pairs (NoSink above: none), its type deduced from the argument.
-template <bool DOM, class Acc, bool MB = false, bool KC = false, class Sink = NoSink>
+// cov: the covariate mode (NoCov above: off; every instantiation without it compiles to the plain epilogue).
+template <class Cov>
+__device__ __forceinline__ R2Adj cov_r2adj(double n_org, const Cov& cov) {
+    if constexpr (Cov::ON) return R2Adj(n_org, cov.n_adj);
+    else return R2Adj(n_org);
+}
+template <bool DOM, class Acc, bool MB = false, bool KC = false, class Sink = NoSink, class Cov = NoCov>
 __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpConst* cst, int rb, int cb, bool diag,
                                               int i, int h, const Acc& gxx, const Acc& gxo, const Acc& gox,
                                               const Acc& goo, const Acc& gxh, const Acc& goh, const Acc& ghx,
                                               const Acc& gho, double ld_wind, double n_org, double rsq_thr,
                                               double kslots, int own_lo, int own_hi, int n_snp,
                                               double* __restrict__ l2_acc, double* __restrict__ l2d_acc,
-                                              int* __restrict__ ws_acc, Sink&& sink = Sink{}) {
+                                              int* __restrict__ ws_acc, Sink&& sink = Sink{},
+                                              const Cov& cov = Cov{}) {
     using S = std::remove_reference_t<Sink>;
-    const R2Adj r2adj(n_org);
+    const R2Adj r2adj = cov_r2adj(n_org, cov);
     const int sj = cb + i;
     const SnpSlot cj = info[sj];
     const SnpConst kj = cst[sj];
@@ -1656,8 +1683,10 @@ __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpCons
                 const double oo = MB ? ki.Ob + kj.Ob - kslots + mm : mm;
                 // KC: the item holds a replayed rare variant (ka / kr terms; kept out of the common path, whose
                 // registers are all taken)
-                const double aa = (xx - kj.mu * xo - ki.mu * (ox - kj.mu * oo)) * (ki.isa * kj.isa) +
-                                  (KC ? kj.ka * ki.SA + ki.ka * (kj.SA + kj.ka * n_org) : 0.0);
+                const double aa_p = (xx - kj.mu * xo - ki.mu * (ox - kj.mu * oo)) * (ki.isa * kj.isa) +
+                                    (KC ? kj.ka * ki.SA + ki.ka * (kj.SA + kj.ka * n_org) : 0.0);
+                double aa = aa_p;
+                if constexpr (Cov::ON) aa = (aa_p - cov.d[0][r][cov.lane]) * (cov.isv[si] * cov.isv[sj]);
                 const double r2 = r2adj(aa);
                 sink.additive(r, nij, nji, aa, r2);
                 if (nij) { rv.l2 = r2; rv.cnt = 1; }
@@ -1666,9 +1695,11 @@ __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpCons
                     if (nij && rpj) {  // A_i . R_j -> L2D_i (ldscalc.h:40-46)
                         const double xh = MB ? 0.5 * ((double)gxh[r] - (double)goh[r]) : (double)gxh[r];
                         const double oh = MB ? kj.H - (double)goh[r] : (double)goh[r];
-                        const double ar = (2.0 * xh - kj.beta * xx - kj.c * xo -
-                                           ki.mu * (2.0 * oh - kj.beta * ox - kj.c * oo)) * (ki.isa * kj.is) +
-                                          (KC ? kj.kr * ki.SA + ki.ka * (kj.SR + kj.kr * n_org) : 0.0);
+                        double ar = (2.0 * xh - kj.beta * xx - kj.c * xo -
+                                     ki.mu * (2.0 * oh - kj.beta * ox - kj.c * oo)) * (ki.isa * kj.is) +
+                                    (KC ? kj.kr * ki.SA + ki.ka * (kj.SR + kj.kr * n_org) : 0.0);
+                        if constexpr (Cov::ON)
+                            ar = (ar - cov.gam[sj] * aa_p - cov.d[1][r][cov.lane]) * (cov.isv[si] * cov.isw[sj]);
                         const double rd = r2adj(ar);
                         rv.l2d = rd;
                         rv.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
@@ -1677,9 +1708,11 @@ __device__ __forceinline__ void pair_epilogue(const SnpSlot* info, const SnpCons
                     if (!diag && nji && rpi) {  // R_i . A_j -> L2D_j
                         const double hx = MB ? 0.5 * ((double)ghx[r] - (double)gho[r]) : (double)ghx[r];
                         const double ho = MB ? ki.H - (double)gho[r] : (double)gho[r];
-                        const double ra = (2.0 * hx - ki.beta * xx - ki.c * ox -
-                                           kj.mu * (2.0 * ho - ki.beta * xo - ki.c * oo)) * (ki.is * kj.isa) +
-                                          (KC ? ki.kr * kj.SA + kj.ka * (ki.SR + ki.kr * n_org) : 0.0);
+                        double ra = (2.0 * hx - ki.beta * xx - ki.c * ox -
+                                     kj.mu * (2.0 * ho - ki.beta * xo - ki.c * oo)) * (ki.is * kj.isa) +
+                                    (KC ? ki.kr * kj.SA + kj.ka * (ki.SR + ki.kr * n_org) : 0.0);
+                        if constexpr (Cov::ON)
+                            ra = (ra - cov.gam[si] * aa_p - cov.d[2][r][cov.lane]) * (cov.isw[si] * cov.isv[sj]);
                         const double rd = r2adj(ra);
                         col.l2d += rd;
                         col.cnt += (1 << 8) + (rd > rsq_thr ? 1 << 16 : 0);
@@ -3022,6 +3055,254 @@ __global__ void __launch_bounds__(256) finalize_annot_kernel(
     if (out_l2d != nullptr) out_l2d[o] = d2;
 }
 
+// ---- covariate-adjusted LD scores (cov-LDSC): every genotype vector residualised on the run's covariates ----
+// With Q (N x q, orthonormal columns that sum to 0) the covariate basis, A_j / R_j SNP j's standardised additive /
+// dominance-residual vectors of the stored coding (0 at missing calls): U_j = Q^T A_j, W_j = Q^T R_j,
+// v_j = 1 - |U_j|^2 / N, gamma_j = -(W_j . U_j) / (N v_j), W'_j = W_j - gamma_j U_j, w_j = 1 - |W_j|^2 / N -
+// gamma_j^2 v_j.  A~_j = (A_j - Q U_j) / sqrt(v_j); R~_j = (R_j - Q W_j - gamma_j (A_j - Q U_j)) / sqrt(w_j), the
+// standardised residual of the dominance coding on the intercept, A_j and the covariates.  The stored coding's U_j is
+// the file coding's negated for a flipped row, W_j the same: every adjusted r^2 is that of the file's coding.
+//
+// covar_project_kernel: the plane sums S_p[j][c] = sum over the individuals i whose stored code of SNP j is p of
+// Q[i][c], p = het (10), hom (11), missing (01); the fourth class follows from sum_i Q[i][c] = 0.  An
+// (M x N, 2-bit) x (N x q, fp64) product on v_mfma_f64_16x16x4_f64: A = 16 SNPs x 4 samples of 0 / 1 indicators (one
+// .bed byte of each row: lane l holds SNP l & 15, sample l >> 4 of the byte, PLINK's order), B = those 4 samples x 16
+// covariates, D = 16 SNPs x 16 covariates in fp64 (lane l: covariate l & 15, SNPs (l >> 4) + 4 reg) — the products
+// are exact, only the additions round.  A workgroup of 4 waves takes one 32-SNP block and the K chunks of piece
+// blockIdx.y of P; per chunk (32 bytes of each row, 128 samples) its Q tile (128 samples x 16 NG covariates, NG
+// groups of 16; qt holds the tiles in the order they are read, [chunk][group][sample][16], zero for samples >= N and
+// covariates >= q) goes through LDS once and serves all 32 rows; wave w takes bytes 8 w .. 8 w + 7 of the chunk for
+// both 16-row halves, all NG groups and the three planes (6 NG accumulators of 4 fp64).  Rows' padding slots (pitch
+// padding, the last byte's unused pairs) are 00 in an fp4 run's image and meet Q = 0.  The four waves' sums are added
+// in wave order through LDS, the piece's [32][3][16 NG] block goes to part[piece][block]: covar_finish_kernel adds
+// the pieces in order, so the sums do not depend on timing.
+typedef double f64x4v __attribute__((ext_vector_type(4)));
+constexpr int COV_WG = 256;
+template <int NG>
+__global__ void __launch_bounds__(COV_WG) covar_project_kernel(const uint8_t* __restrict__ img, int row_bytes, int n_it,
+                                                               const double* __restrict__ qt, int P,
+                                                               double* __restrict__ part) {
+    constexpr int QP = 16 * NG;            // padded covariates
+    constexpr int TILE = 128 * QP;         // doubles of one chunk's Q tile
+    __shared__ double qs[TILE];            // [group][sample][16]; afterwards the block's sums [32][3][QP]
+    const int b = blockIdx.x, piece = blockIdx.y;
+    const int t_lo = (int)((long long)piece * n_it / P), t_hi = (int)((long long)(piece + 1) * n_it / P);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, k = lane >> 4;
+    const uint8_t* rows = img + (size_t)b * 32 * (size_t)row_bytes + 8 * w;
+    f64x4v acc[2][NG][3];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) acc[hf][g][p] = f64x4v{0.0, 0.0, 0.0, 0.0};
+    // (native vector types: the registers below must not go through private memory)
+    typedef double f64x2v __attribute__((ext_vector_type(2)));
+    typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
+    f64x2v qreg[4 * NG];
+    u32x2v a0 = {0u, 0u}, a1 = {0u, 0u};
+    // iteration t stages and consumes chunk t (fetched into registers one iteration earlier) and fetches chunk t + 1:
+    // its share of the Q tile and the wave's 8 bytes of rows c and 16 + c
+    for (int t = t_lo - 1; t < t_hi; ++t) {
+        const bool cur = t >= t_lo;  // (uniform over the workgroup)
+        u32x2v c0 = {0u, 0u}, c1 = {0u, 0u};
+        if (cur) {
+            __syncthreads();  // (the chunk before is read)
+#pragma unroll
+            for (int u = 0; u < 4 * NG; ++u) reinterpret_cast<f64x2v*>(qs)[u * COV_WG + tid] = qreg[u];
+            c0 = a0, c1 = a1;
+            __syncthreads();
+        }
+        if (t + 1 < t_hi) {
+            const f64x2v* src = reinterpret_cast<const f64x2v*>(qt + (size_t)(t + 1) * TILE);
+#pragma unroll
+            for (int u = 0; u < 4 * NG; ++u) qreg[u] = src[u * COV_WG + tid];
+            a0 = *reinterpret_cast<const u32x2v*>(rows + (size_t)(t + 1) * 1024 + c * 32);
+            a1 = *reinterpret_cast<const u32x2v*>(rows + (size_t)(t + 1) * 1024 + (16 + c) * 32);
+        }
+        if (!cur) continue;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int sh8 = 8 * (j & 3) + 2 * k;
+            const uint32_t code[2] = {((j < 4 ? c0.x : c0.y) >> sh8) & 3u, ((j < 4 ? c1.x : c1.y) >> sh8) & 3u};
+            double ind[2][3];
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                ind[hf][0] = code[hf] == 2u ? 1.0 : 0.0;  // het
+                ind[hf][1] = code[hf] == 3u ? 1.0 : 0.0;  // stored hom (11)
+                ind[hf][2] = code[hf] == 1u ? 1.0 : 0.0;  // missing
+            }
+            const int sl = 4 * (8 * w + j) + k;  // the sample's slot in the chunk
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                const double bq = qs[(g * 128 + sl) * 16 + c];
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                    for (int p = 0; p < 3; ++p)
+                        acc[hf][g][p] = __builtin_amdgcn_mfma_f64_16x16x4f64(ind[hf][p], bq, acc[hf][g][p], 0, 0, 0);
+            }
+        }
+    }
+    // the four waves' sums, added in wave order: red[row][plane][covariate]
+    double* red = qs;
+    for (int ww = 0; ww < 4; ++ww) {
+        __syncthreads();
+        if (w == ww) {
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+#pragma unroll
+                    for (int p = 0; p < 3; ++p)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int at = ((16 * hf + k + 4 * r) * 3 + p) * QP + 16 * g + c;
+                            red[at] = (ww == 0 ? 0.0 : red[at]) + acc[hf][g][p][r];
+                        }
+        }
+    }
+    __syncthreads();
+    double* out = part + ((size_t)piece * gridDim.x + b) * (size_t)(96 * QP);
+    for (int at = tid; at < 96 * QP; at += COV_WG) out[at] = red[at];
+}
+
+// Per SNP, from the plane sums (the P pieces added in order) and the stored coding's moments (coding_moments of the
+// stored counts, the constants of cst): U, W, W' to cu / cw / cwp ([q][n_snp]), and csc[k * n_snp + j], k = 0 isv
+// (1 / sqrt(v), 0 for v < 1e-6: A~ := 0), 1 gamma (0 then), 2 isw (1 / sqrt(w), 0 for w < 1e-6 or a residual of std
+// 0: R~ := 0), 3 v, 4 w; the residual std output becomes rstd sqrt(w) and flag bit 1 (residual pass) is taken on it.
+// SNPs that failed MAF, are unused or have every call missing keep U = W = 0, v = w = 1 and their outputs.
+__global__ void __launch_bounds__(256) covar_finish_kernel(const double* __restrict__ part, int P, int nblk, int QP,
+                                                           int n_covar, const int* __restrict__ counts,
+                                                           int n_snp, int n_org, double std_thr,
+                                                           uint8_t* __restrict__ sflags, double* __restrict__ rstd_out,
+                                                           double* __restrict__ cu, double* __restrict__ cw,
+                                                           double* __restrict__ cwp, double* __restrict__ csc) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_snp) return;
+    const uint8_t fl = sflags[j];
+    const double s0 = counts[4 * (size_t)j], c1 = counts[4 * (size_t)j + 1], s2 = counts[4 * (size_t)j + 2];
+    const double N = (double)n_org;
+    const bool live = (fl & 1) && s0 + c1 + s2 > 0.0;
+    double isv = 1.0, gam = 0.0, isw = 1.0, v = 1.0, wv = 1.0;
+    if (live) {
+        const Coding m = coding_moments(s0, c1, s2, N);  // the stored coding
+        const double cc = m.dbar - m.beta * m.abar;
+        const double* sums = part + ((size_t)(j >> 5) * 96 + (size_t)(j & 31) * 3) * QP;
+        const size_t piece_stride = (size_t)nblk * 96 * QP;
+        double uu = 0.0, ww = 0.0, uw = 0.0;
+        for (int c = 0; c < n_covar; ++c) {
+            double sh = 0.0, so = 0.0, sm = 0.0;
+            for (int p = 0; p < P; ++p) {
+                const double* q = sums + (size_t)p * piece_stride + c;
+                sh += q[0];
+                so += q[QP];
+                sm += q[2 * QP];
+            }
+            const double u = (sh + 2.0 * so + m.abar * sm) / m.sd_a;
+            const double wc = m.rstd > 0.0 ? (2.0 * (sh + so) - m.beta * (sh + 2.0 * so) + cc * sm) / m.rstd : 0.0;
+            cu[(size_t)c * n_snp + j] = u;
+            cw[(size_t)c * n_snp + j] = wc;
+            uu += u * u;
+            ww += wc * wc;
+            uw += u * wc;
+        }
+        v = 1.0 - uu / N;
+        if (v < 1e-6) isv = 0.0;
+        else {
+            isv = 1.0 / sqrt(v);
+            gam = -uw / (N * v);
+        }
+        wv = 1.0 - ww / N - gam * gam * v;
+        if (wv < 1e-6 || !(m.rstd > 0.0)) isw = 0.0;
+        else isw = 1.0 / sqrt(wv);
+        for (int c = 0; c < n_covar; ++c)
+            cwp[(size_t)c * n_snp + j] = cw[(size_t)c * n_snp + j] - gam * cu[(size_t)c * n_snp + j];
+        const double rstd = isw != 0.0 ? rstd_out[j] * sqrt(wv) : 0.0;
+        rstd_out[j] = rstd;
+        sflags[j] = (uint8_t)((fl & ~2) | ((fl & 2) && rstd > std_thr ? 2 : 0));
+    } else {
+        for (int c = 0; c < n_covar; ++c) {
+            cu[(size_t)c * n_snp + j] = 0.0;
+            cw[(size_t)c * n_snp + j] = 0.0;
+            cwp[(size_t)c * n_snp + j] = 0.0;
+        }
+    }
+    csc[j] = isv;
+    csc[(size_t)n_snp + j] = gam;
+    csc[2 * (size_t)n_snp + j] = isw;
+    csc[3 * (size_t)n_snp + j] = v;
+    csc[4 * (size_t)n_snp + j] = wv;
+}
+
+// The K-split epilogue of a covariate run: band_f4_epi_kernel with pair_epilogue in its covariate mode.  After
+// load_split_item the q-length dot products of the lane's 16 pairs accumulate over chunks of COV_CHUNK covariates
+// whose U and W' of the item's 64 slots are staged through LDS (as the annotated epilogue stages its weights), in
+// covariate order — a pair's products and their order do not depend on the item or the batch — and go to the LDS
+// tiles pair_epilogue reads.  No KC instantiation: a covariate run takes the closed-form vectors of rare variants
+// (NLDSC_FLAG_EXACT_RARE) and has no replayed SNP.
+constexpr int COV_CHUNK = 16;
+template <bool DOM>
+__global__ void __launch_bounds__(64) band_f4_epi_cov_kernel(
+    const SnpConst* __restrict__ cst, const int4* __restrict__ items, const double* __restrict__ pos,
+    const int* __restrict__ Lw, const int* __restrict__ Rw, const uint8_t* __restrict__ sflags, int n_snp,
+    double ld_wind, double n_org, double rsq_thr, int own_lo, int own_hi, double* __restrict__ l2_acc,
+    double* __restrict__ l2d_acc, int* __restrict__ ws_acc, int P, const float* __restrict__ gram,
+    const double* __restrict__ cu, const double* __restrict__ cwp, const double* __restrict__ csc, int n_covar) {
+    __shared__ SlotLds<64> sh;
+    __shared__ float tr[32 * 33];
+    __shared__ double dt[DOM ? 3 : 1][16][64];  // CovTiles::d
+    __shared__ double uc[64][COV_CHUNK + 1], wc[64][COV_CHUNK + 1];  // a chunk's U / W' of the 64 slots
+    __shared__ double sc[3][64];  // isv, gamma, isw of the 64 slots
+    const int4 it = items[blockIdx.x];
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    f32x16v g8[8];
+    const SnpSlot mine = load_split_item(sh.info, sh.cst, tr, g8, it, cst, pos, Lw, Rw, sflags, n_snp, P, gram);
+    const int g = mine.g;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sc[k][lane] = g < n_snp ? csc[(size_t)k * n_snp + g] : 0.0;
+    double d0[16], d1[16], d2[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) d0[r] = d1[r] = d2[r] = 0.0;
+    const int sj = 32 + i;
+    for (int c0 = 0; c0 < n_covar; c0 += COV_CHUNK) {
+        __syncthreads();  // (the chunk before is read)
+#pragma unroll
+        for (int cc = 0; cc < COV_CHUNK; ++cc) {
+            const bool in = c0 + cc < n_covar && g < n_snp;
+            uc[lane][cc] = in ? cu[(size_t)(c0 + cc) * n_snp + g] : 0.0;
+            wc[lane][cc] = in ? cwp[(size_t)(c0 + cc) * n_snp + g] : 0.0;
+        }
+        __syncthreads();
+        for (int cc = 0; cc < COV_CHUNK; ++cc) {
+            const double uj = uc[sj][cc], wj = wc[sj][cc];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int si = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const double ui = uc[si][cc];
+                d0[r] += ui * uj;
+                if (DOM) {
+                    d1[r] += ui * wj;
+                    d2[r] += wc[si][cc] * uj;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {  // (each lane reads back only what it wrote)
+        dt[0][r][lane] = d0[r];
+        if (DOM) {
+            dt[1][r][lane] = d1[r];
+            dt[2][r][lane] = d2[r];
+        }
+    }
+    __syncthreads();  // (sc of every slot)
+    const CovTiles cov{dt, sc[0], sc[1], sc[2], n_org - (double)n_covar, lane};
+    pair_epilogue<DOM, f32x16v, true, false>(sh.info, sh.cst, 0, 32, it.x == it.y, i, h, g8[0], g8[1], g8[2], g8[3], g8[4],
+                                             g8[5], g8[6], g8[7], ld_wind, n_org, rsq_thr, n_org, own_lo, own_hi, n_snp,
+                                             l2_acc, l2d_acc, ws_acc, NoSink{}, cov);
+}
+
 // ---- the pairwise LD table: the (k, r, rd) of every ordered pair (j, k) the plain run counts in WSA[j] ----
 // A pairs run sends every block pair through band_f4_part_kernel and then through band_f4_epi_pairs_kernel, which runs
 // the plain epilogue's pair_epilogue with PairsSink as its sink (with EMIT = false it adds the ordinary sums, a plain
@@ -3690,6 +3971,42 @@ hipError_t launch_band_f4_annot(const BandArgs& a, const AnnotArgs& an, int P, c
                        an.l2c_lo, an.l2dc_lo)
     if (a.dom) NLDSC_EPI(true, false); else NLDSC_EPI(false, false);
     if (a.blk_rep) { if (a.dom) NLDSC_EPI(true, true); else NLDSC_EPI(false, true); }
+#undef NLDSC_EPI
+    return hipGetLastError();
+}
+
+int covar_groups(int n_covar) { return std::min(std::max((n_covar + 15) / 16, 1), 4); }
+
+int covar_pieces(int nblk, int n_it, int n_cu) {
+    // two workgroups per CU's worth of work at least, a piece of 4 chunks at least
+    const int want = (4 * n_cu + nblk - 1) / std::max(nblk, 1);
+    return std::max(1, std::min(want, std::max(n_it / 4, 1)));
+}
+
+hipError_t launch_covar_project(const uint8_t* img, int row_bytes, int n_snp, int n_org, const int* counts,
+                                double std_thr, const CovArgs& cv, int P, uint8_t* sflags, double* rstd_out,
+                                hipStream_t st) {
+    const int NG = covar_groups(cv.n_covar), nblk = (n_snp + 31) / 32, n_it = row_bytes / 32;
+    if (cv.n_covar < 1 || cv.n_covar > 64 || P < 1 || P > n_it) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nblk, (unsigned)P);
+#define NLDSC_PROJ(NG_)                                                                                              \
+    hipLaunchKernelGGL((covar_project_kernel<NG_>), grid, dim3(COV_WG), 0, st, img, row_bytes, n_it, cv.qt, P, cv.part)
+    if (NG == 1) NLDSC_PROJ(1); else if (NG == 2) NLDSC_PROJ(2); else if (NG == 3) NLDSC_PROJ(3); else NLDSC_PROJ(4);
+#undef NLDSC_PROJ
+    hipLaunchKernelGGL(covar_finish_kernel, dim3((n_snp + 255) / 256), dim3(256), 0, st, cv.part, P, nblk, 16 * NG,
+                       cv.n_covar, counts, n_snp, n_org, std_thr, sflags, rstd_out, cv.u, cv.w, cv.wp, cv.sc);
+    return hipGetLastError();
+}
+
+hipError_t launch_band_f4_cov(const BandArgs& a, const CovArgs& cv, int P, const int4* items, int n_items,
+                              float* gram) {
+    if (n_items <= 0) return hipSuccess;
+    if (cv.n_covar < 1 || cv.n_covar > 64 || a.blk_rep != nullptr) return hipErrorInvalidValue;
+    if (launch_f4_part(a, P, items, n_items, gram, nullptr) != hipSuccess) return hipErrorInvalidValue;
+#define NLDSC_EPI(DOM_)                                                                                              \
+    hipLaunchKernelGGL((band_f4_epi_cov_kernel<DOM_>), dim3(n_items), dim3(64), 0, a.st, a.cst, items, A_SNPS, A_EPI, \
+                       P, gram, cv.u, cv.wp, cv.sc, cv.n_covar)
+    if (a.dom) NLDSC_EPI(true); else NLDSC_EPI(false);
 #undef NLDSC_EPI
     return hipGetLastError();
 }

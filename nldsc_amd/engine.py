@@ -118,11 +118,15 @@ class Engine:
         self._loaded(n_snp, n_org)
 
     # ---- compute ------------------------------------------------------------------------
-    def run(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, out=None, annot=None):
+    def run(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, out=None, annot=None,
+            covar=None):
         """LD scores for owned SNPs [own[0], own[1]) (default all).  Returns dict of numpy arrays
         (entries outside the owned range are NaN / -1, or whatever `out` held).  `annot`: an [n_snp, C] annotation
         matrix (C ABI nldsc_engine_run_annot); the dict then also holds "l2_annot" and "l2d_annot", [n_snp, C]
-        float64 (taken from `out` when it has them, category-major [C, n_snp] contiguous arrays viewed transposed)."""
+        float64 (taken from `out` when it has them, category-major [C, n_snp] contiguous arrays viewed transposed).
+        `covar`: an [n_org, q] orthonormal basis of the centred covariates (ldscore.common.covar_basis), row i = the
+        image's individual i: covariate-adjusted LD scores (C ABI nldsc_engine_run_covar), in PLINK's sample order
+        (the flag is set); not together with `annot`."""
         n = self.n_snp
         own = (0, n) if own is None else own
         p, _keep = _lib.make_params(n, self.n_org, ld_wind, maf, std_thr, rsq_thr, positions, flags=flags)
@@ -134,6 +138,15 @@ class Engine:
             res = _lib.Result(*(arrs[k].ctypes.data_as(d if arrs[k].dtype == np.float64 else i)
                                 for k in ("l2", "l2d", "maf", "residuals_std", "l2_ws", "l2d_ws", "l2d_wse")))
         err = _lib.errbuf()
+        if covar is not None:
+            if annot is not None:
+                raise _lib.NLDSCError(_lib.E_ARG,
+                                      "covariates with annotations or a pair table in one run are not supported")
+            q = _lib.covar_basis_matrix(covar, self.n_org)
+            p.flags |= _lib.FLAG_STRICT_PLINK_ORDER
+            _lib.check(self._L.nldsc_engine_run_covar(self._h, ctypes.byref(p), q.ctypes.data, q.shape[0],
+                                                      int(own[0]), int(own[1]), ctypes.byref(res), err, len(err)), err)
+            return arrs
         if annot is not None:
             a = _lib.annot_matrix(annot, n)
             for k in ("l2_annot", "l2d_annot"):
@@ -148,6 +161,19 @@ class Engine:
         _lib.check(self._L.nldsc_engine_run(self._h, ctypes.byref(p), int(own[0]), int(own[1]),
                                                ctypes.byref(res), err, len(err)), err)
         return arrs
+
+    def covar_projections(self, n_covar: int) -> dict:
+        """The projections of the last covariate run (C ABI nldsc_engine_covar_projections): "u", "w" [n_snp, q]
+        (U_j = Q^T A_j in the file's allele coding, W_j = Q^T R_j), "v", "wd" [n_snp] (the shares of the additive /
+        dominance-residual variance the covariates leave)."""
+        n, q = self.n_snp, int(n_covar)
+        u, w = np.empty((q, n)), np.empty((q, n))
+        v, wd = np.empty(n), np.empty(n)
+        rc = self._L.nldsc_engine_covar_projections(self._h, u.ctypes.data, w.ctypes.data, v.ctypes.data,
+                                                    wd.ctypes.data)
+        if rc != _lib.OK:
+            raise _lib.NLDSCError(rc, "no covariate run to report projections of")
+        return dict(u=u.T, w=w.T, v=v, wd=wd)
 
     def size_pairs(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, min_r2=None):
         """The sizing call of `run_pairs` alone (C ABI nldsc_engine_run_pairs without arrays): the usual dict plus
@@ -267,14 +293,24 @@ class Engine:
 
 
 def calculate(bedfile: str, n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, *, flags=0, device=-1,
-              keep=None, annot=None) -> dict:
+              keep=None, annot=None, covar=None) -> dict:
     """One-shot C-ABI call `nldsc_ld_calculate` (file -> GPU -> results); with `keep` (0-based .fam line numbers,
     strictly ascending; n_org stays the file's count) `nldsc_ld_calculate_keep`, on those individuals only; with
-    `annot` ([n_snp, C]) `nldsc_ld_calculate_annot`, which adds "l2_annot" and "l2d_annot" ([n_snp, C])."""
+    `annot` ([n_snp, C]) `nldsc_ld_calculate_annot`, which adds "l2_annot" and "l2d_annot" ([n_snp, C]); with `covar`
+    (an orthonormal basis, one row per individual the run uses) `nldsc_ld_calculate_covar`."""
     p, _pos = _lib.make_params(n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, bedfile=bedfile,
                                flags=flags, device=device)
     arrs, res = _lib.alloc_result(n_snp)
     err = _lib.errbuf()
+    if covar is not None:
+        if annot is not None:
+            raise _lib.NLDSCError(_lib.E_ARG, "covariates with annotations or a pair table in one run are not supported")
+        idx = None if keep is None or len(keep) == 0 else np.ascontiguousarray(keep, dtype=np.int32)
+        q = _lib.covar_basis_matrix(covar, n_org if idx is None else len(idx))
+        _lib.check(_lib.lib().nldsc_ld_calculate_covar(
+            ctypes.byref(p), None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx), q.ctypes.data,
+            q.shape[0], ctypes.byref(res), err, len(err)), err)
+        return arrs
     if annot is not None:
         a = _lib.annot_matrix(annot, n_snp)
         idx = None if keep is None or len(keep) == 0 else np.ascontiguousarray(keep, dtype=np.int32)

@@ -8,6 +8,7 @@ The reference's public names, validation rules and messages, 
                          counterpart: PLINK's / LDSC's flags of the same names)
   AnnotFile              LDSC's .annot / .annot.gz (partitioned LD scores, --annot): names + an [M, C] float64 matrix
   r2_adjusted            the adjusted r-squared of a correlation, in the engine's fp64 expression (--pairs-out)
+  CovarFile, covar_basis PLINK's covariate file (--covar) and the orthonormal basis of its columns the engine takes
   MAF, ResidualsSTDThreshold, RSQThreshold: [0, 1), [0, 1), [0, 0.1)
 (RSQThreshold's repr says `std_thr=`, as the reference's does.)
 """
@@ -23,7 +24,8 @@ from ..core.common import Data, NLDSCParameterError
 from ..core.logger import log
 
 __all__ = ["LDWindow", "PLINKFile", "BEDFile", "BIMFile", "FAMFile", "MAF", "ResidualsSTDThreshold",
-           "RSQThreshold", "NLDSCParameterError", "read_id_file", "kept_individuals", "AnnotFile", "r2_adjusted"]
+           "RSQThreshold", "NLDSCParameterError", "read_id_file", "kept_individuals", "AnnotFile", "r2_adjusted",
+           "CovarFile", "covar_basis"]
 
 # window metric -> (largest window, how the message names it)
 _WINDOW_LIMITS = {"bp": (5 * 10 ** 6, "5 Mbp"), "cm": (100, "100 cm")}
@@ -227,6 +229,133 @@ class AnnotFile(Data):
             k, c = bad[0]
             raise NLDSCParameterError(f"{where}, row {k + 1}, column {self._names[c]}: the value is not finite")
         self._data = data
+
+
+class CovarFile(Data):
+    """PLINK's covariate file (--covar): whitespace-separated `FID IID c1 c2 ...`, one individual per line.  A first
+    line whose third field is not a number (nor NA) is a header naming the columns; without one they are COV1, COV2,
+    ...  `names`: the covariate columns' names; `ids`: the (FID, IID) of every row; `matrix(ids)`: the rows of the
+    given individuals, in their order, as an [n, c] float64 matrix.  A duplicate (FID, IID) is an error when the file
+    is read; the values are checked for the rows a run uses (rows of other individuals are ignored, so individuals
+    with missing covariates can be left out with --keep / --remove)."""
+    MISSING = ("NA", "NAN", "N/A", ".")
+
+    def __init__(self, path: str):
+        self._path = str(path)
+        if not os.path.exists(self._path):
+            raise FileNotFoundError(f'No such file: "{self._path}"')
+        with open(self._path, "rt") as fh:
+            self._lines = [(n, f) for n, f in ((n, line.split()) for n, line in enumerate(fh, 1)) if f]
+        self._validate()
+        del self._lines
+        self._data = self._path
+
+    def _validate(self):
+        rows, where = self._lines, f'"{self._path}"'
+        if not rows:
+            raise NLDSCParameterError(f"{where}: the covariate file is empty")
+        for n, f in rows:
+            if len(f) < 3:
+                raise NLDSCParameterError(f'{where}, line {n}: expected "FID IID c1 ...", got fewer than three fields')
+        first = rows[0][1]
+        header = not (_is_number(first[2]) or first[2].upper() in self.MISSING)
+        width = len(first)
+        self._names = first[2:] if header else [f"COV{k + 1}" for k in range(width - 2)]
+        if header:
+            rows = rows[1:]
+            dup = sorted({n for n in self._names if self._names.count(n) > 1})
+            if dup:
+                raise NLDSCParameterError(f"{where}: duplicate covariate column name {dup[0]}")
+        self._rows = {}
+        for n, f in rows:
+            if len(f) != width:
+                raise NLDSCParameterError(f"{where}, line {n}: {len(f)} fields, expected {width}")
+            key = (f[0], f[1])
+            if key in self._rows:
+                raise NLDSCParameterError(f"{where}, line {n}: a second row for individual {f[0]} {f[1]} (the first "
+                                          f"is line {self._rows[key][0]})")
+            self._rows[key] = (n, f[2:])
+
+    @property
+    def names(self) -> list:
+        return list(self._names)
+
+    @property
+    def ids(self) -> list:
+        return list(self._rows)
+
+    def __repr__(self):
+        return f"CovarFile(path='{self._path}', n_covar={len(self._names)}, rows={len(self._rows)})"
+
+    def matrix(self, ids) -> np.ndarray:
+        """The covariates of the individuals `ids` ((FID, IID) pairs: the .fam lines a run uses), row k = ids[k].
+        Every one of them needs a row whose values are all numeric and finite; the error names the first that does
+        not and advises --keep."""
+        where = f'"{self._path}"'
+        advice = "give every individual of the run a complete row, or leave such individuals out with --keep / --remove"
+        out = np.empty((len(ids), len(self._names)), dtype=np.float64)
+        for k, key in enumerate(ids):
+            row = self._rows.get(tuple(key))
+            if row is None:
+                raise NLDSCParameterError(f"{where}: no row for individual {key[0]} {key[1]} (.fam line {k + 1} of "
+                                          f"the run's individuals): {advice}")
+            n, fields = row
+            for c, text in enumerate(fields):
+                if text.upper() in self.MISSING:
+                    raise NLDSCParameterError(f"{where}, line {n}: covariate {self._names[c]} of individual {key[0]} "
+                                              f"{key[1]} is missing ({text}): {advice}")
+                if not _is_number(text):
+                    raise NLDSCParameterError(f"{where}, line {n}: non-numeric value {text!r} for covariate "
+                                              f"{self._names[c]} of individual {key[0]} {key[1]}: {advice}")
+                value = float(text)
+                if not np.isfinite(value):
+                    raise NLDSCParameterError(f"{where}, line {n}: covariate {self._names[c]} of individual {key[0]} "
+                                              f"{key[1]} is not finite ({text}): {advice}")
+                out[k, c] = value
+        return out
+
+
+def covar_basis(covar, tol: float = 1e-10):
+    """The orthonormal basis the engine takes for a covariate matrix `covar` ([N, c]; a 1-D array is one column):
+    every column centred and scaled to unit norm (a constant column becomes 0), then the left singular vectors whose
+    singular value exceeds `tol` times the largest.  Returns (Q [N, q] float64, dropped): q is the numerical rank of
+    the centred matrix, Q's columns sum to 0, and `dropped` lists the indices of the columns that add nothing to the
+    columns before them (constant, or linearly dependent on them) — len(dropped) == c - q whenever the two rank
+    decisions agree (they are taken at the same tolerance).  Q depends on the covariates' column space only: scaling
+    columns, adding constants or mixing them by an invertible matrix gives a basis of the same space."""
+    c = np.asarray(covar, dtype=np.float64)
+    if c.ndim == 1:
+        c = c[:, None]
+    if c.ndim != 2:
+        raise ValueError(f"covar must be an [N, c] matrix, got shape {c.shape}")
+    if not np.isfinite(c).all():
+        raise NLDSCParameterError("a covariate value is not finite")
+    n, k = c.shape
+    scale = np.abs(c).max(axis=0) if n else np.zeros(k)
+    c = c - c.mean(axis=0)
+    c = c - c.mean(axis=0)  # (the first mean's rounding, large against a column with a big constant added)
+    norm = np.sqrt((c * c).sum(axis=0))
+    # a constant column is 0 after centring up to the rounding of its mean: at most ~N eps |x|
+    live = norm > 64 * n * np.finfo(np.float64).eps * np.maximum(scale, np.finfo(np.float64).tiny)
+    c = np.where(live, c / np.where(live, norm, 1.0), 0.0)
+    if k == 0 or not live.any():
+        return np.zeros((n, 0)), list(range(k))
+    u, s, _ = np.linalg.svd(c, full_matrices=False)
+    q = u[:, : int((s > tol * s[0]).sum())]
+    q = q - q.mean(axis=0)  # (sums of ~1e-16 sqrt(N): exactly centred to the last rounding)
+    # which columns drop out: those the columns before them already span (Gram-Schmidt, twice for orthogonality)
+    dropped, basis = [], np.zeros((n, 0))
+    for j in range(k):
+        r = c[:, j]
+        if live[j]:
+            for _ in range(2):
+                r = r - basis @ (basis.T @ r)
+        rn = float(np.sqrt(r @ r))
+        if not live[j] or rn <= tol:
+            dropped.append(j)
+        else:
+            basis = np.concatenate([basis, (r / rn)[:, None]], axis=1)
+    return np.ascontiguousarray(q), dropped
 
 
 def _is_number(text: str) -> bool:

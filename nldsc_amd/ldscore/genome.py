@@ -20,8 +20,9 @@ from ..core.common import NLDSCParameterError, elapsed_time
 from ..core.logger import log
 from .common import (AnnotFile, FAMFile, BIMFile, LDWindow, MAF, ResidualsSTDThreshold, RSQThreshold,
                      kept_individuals)
-from .routine import (PAIRS_BUDGET, annot_output, m_annot_values, m_values, make_output, reject_pairs_options,
-                      reject_sharded_annot, run_pairs_to_file, write_m_annot_file, write_m_file, write_scores)
+from .routine import (PAIRS_BUDGET, annot_output, covar_basis_of_run, m_annot_values, m_values, make_output,
+                      reject_covar_options, reject_pairs_options, reject_sharded_annot, run_pairs_to_file,
+                      write_m_annot_file, write_m_file, write_scores)
 
 CHROMS = [str(c) for c in range(1, 23)] + ["X", "Y", "XY", "MT"]
 
@@ -84,8 +85,10 @@ def _default_runner(device: int, keep=None, n_org_file: int = 0):
         eng.set_keep(keep, n_org_file)
 
     def run(bed_path: str, n_snp: int, n_org: int, ld_wind, maf, std_thr, rsq_thr, positions, flags, annot=None,
-            pairs=None):
+            pairs=None, covar=None):
         eng.load_bed_file(bed_path, n_snp, n_org)
+        if covar is not None:  # (--covar: the orthonormal basis, one row per individual of the image)
+            return eng.run(ld_wind, maf, std_thr, rsq_thr, positions, flags=flags, covar=covar), eng.timings()
         if pairs is not None:  # (--pairs-out: dict(path, bim, min_r2, budget))
             return run_pairs_to_file(eng, ld_wind, maf, std_thr, rsq_thr, positions, flags, **pairs), eng.timings()
         return eng.run(ld_wind, maf, std_thr, rsq_thr, positions, flags=flags, annot=annot), eng.timings()
@@ -100,14 +103,19 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
                         runner=None, rank: int | None = None, world: int | None = None,
                         progress: bool | None = None, keep: str | None = None,
                         remove: str | None = None, annot: str | None = None, pairs_out: str | None = None,
-                        pairs_min_r2: float | None = None, pairs_budget: int = PAIRS_BUDGET) -> dict:
+                        pairs_min_r2: float | None = None, pairs_budget: int = PAIRS_BUDGET,
+                        covar: str | None = None) -> dict:
     """Returns {chromosome: output DataFrame (None when written to `out`)} for the chromosomes this rank
     processed.  `keep` / `remove`: `FID IID` lists as in estimate_lds; every chromosome's .fam must resolve to the
     same individuals (a `runner` given by the caller then receives them as the keyword `keep`).  `annot`: an LDSC
     `.annot` / `.annot.gz` path with '@' in place of the chromosome, as in `bfile` (a runner then receives each
     chromosome's [M, C] matrix as the keyword `annot`).  `pairs_out`: a path with '@' for each chromosome's pairwise
     LD table, as in estimate_lds (a runner then receives dict(path, bim, min_r2, budget) as the keyword `pairs` and
-    writes the table itself)."""
+    writes the table itself).  `covar`: one PLINK covariate file for every chromosome, as in estimate_lds: the basis is
+    built once, for the first chromosome's .fam — with `covar` every chromosome's .fam must list the same individuals
+    in the same order (a runner then receives the [n, q] basis as the keyword `covar`)."""
+    if covar is not None:
+        reject_covar_options(annot, pairs_out, sharded_ok=True)
     if pairs_out is not None:
         reject_pairs_options(annot)
         if "@" not in pairs_out:
@@ -127,8 +135,15 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
     from ..distributed import assign_units, window_work
     meta = []
     kept, kept_n_file = None, 0
+    fam0 = None  # (--covar: the first chromosome's .fam, whose individuals the basis rows are)
     for chrom, stem in units:
         bim, fam = BIMFile(stem + ".bim"), FAMFile(stem + ".fam")
+        if covar is not None:
+            if fam0 is None:
+                fam0 = fam
+            elif fam.ids != fam0.ids:
+                raise NLDSCParameterError(f"--covar: {stem}.fam lists other individuals (or another order) than "
+                                          f"{units[0][1]}.fam: every chromosome needs the same .fam")
         if keep is not None or remove is not None:
             k = kept_individuals(fam, keep, remove)
             if kept is None:
@@ -140,6 +155,7 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
         pos = np.asarray(getattr(bim, ld_wind_.metric), dtype=np.float64)
         meta.append(dict(chrom=chrom, stem=stem, bim=bim, n_org=fam.n_org, pos=pos,
                          work=float(window_work(pos, ld_wind_.data).sum()) * fam.n_org))
+    covar_kw = {} if covar is None else {"covar": covar_basis_of_run(covar, fam0, kept)}
     mine = assign_units([m["work"] for m in meta], world)[rank]
     log.info(f"[rank {rank}/{world}] {len(mine)} of {len(units)} chromosomes: "
              f"{', '.join(meta[u]['chrom'] for u in mine)}")
@@ -184,7 +200,7 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
             annot_kw["pairs"] = dict(path=pairs_out.replace("@", m["chrom"]), bim=m["bim"], min_r2=pairs_min_r2,
                                      budget=pairs_budget)
         res, tim = runner(bed, n_snp, m["n_org"], ld_wind_.data, maf_thr_.data, std_thr_.data, rsq, m["pos"], flags,
-                          **kept_kw, **annot_kw)
+                          **kept_kw, **annot_kw, **covar_kw)
         ld = _Res(res)
         names = annot_.names if annot_ is not None else None
         if out is None:

@@ -18,12 +18,13 @@ from ..core.common import elapsed_time
 from ..core.logger import log
 from . import _ldscore as lds
 from ..core.common import NLDSCParameterError
-from .common import (AnnotFile, BIMFile, LDWindow, MAF, PLINKFile, ResidualsSTDThreshold, RSQThreshold,
-                     kept_individuals, r2_adjusted)
+from .common import (AnnotFile, BIMFile, CovarFile, LDWindow, MAF, PLINKFile, ResidualsSTDThreshold, RSQThreshold,
+                     covar_basis, kept_individuals, r2_adjusted)
 
 __all__ = ["estimate_lds", "make_output", "format_scores", "write_scores", "show_summary", "m_values", "write_m_file",
            "annot_output", "m_annot_values", "write_m_annot_file", "reject_sharded_annot", "reject_pairs_options",
-           "PAIRS_HEADER", "PAIRS_BUDGET", "open_pairs", "write_pairs", "run_pairs_to_file"]
+           "PAIRS_HEADER", "PAIRS_BUDGET", "open_pairs", "write_pairs", "run_pairs_to_file", "reject_covar_options",
+           "covar_basis_of_run"]
 
 
 def show_summary(ld) -> None:
@@ -146,6 +147,34 @@ def reject_pairs_options(annot: str | None) -> None:
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NLDSCParameterError("--pairs-out (the pairwise LD table) runs on one GPU: launch it without torchrun, "
                                   "or with one rank")
+
+
+def reject_covar_options(annot: str | None, pairs_out: str | None, *, sharded_ok: bool = False) -> None:
+    """--covar with --annot or --pairs-out (the engine's message: partitioned and pairwise covariate-adjusted output
+    is not built), or under torchrun with more than one rank on one chromosome (the ranks' shards would each need
+    the basis; a whole-genome run gives every rank whole chromosomes and is fine)."""
+    if annot is not None or pairs_out is not None:
+        raise NLDSCParameterError("--covar cannot be combined with --annot or --pairs-out: covariates with "
+                                  "annotations or a pair table in one run are not supported")
+    if not sharded_ok and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NLDSCParameterError("--covar (covariate-adjusted LD scores) runs a chromosome on one GPU: launch it "
+                                  "without torchrun, or with one rank")
+
+
+def covar_basis_of_run(covar: str, fam, kept) -> np.ndarray:
+    """The orthonormal basis Q ([n, q]) of the covariate file `covar` for a run on the .fam lines `kept` (None:
+    everyone) of `fam`: its rows matched to those individuals by (FID, IID), in .fam order (CovarFile.matrix), then
+    common.covar_basis.  Logs the covariates read, the rank kept and the columns dropped."""
+    cf = CovarFile(covar)
+    fam_ids = fam.ids
+    ids = fam_ids if kept is None else [fam_ids[int(s)] for s in kept]
+    q, dropped = covar_basis(cf.matrix(ids))
+    names = cf.names
+    log.info(f"Covariates: c = {len(names)} columns of {covar} for {len(ids)} individuals, q = {q.shape[1]} kept"
+             + (f"; dropped (constant or dependent): {', '.join(names[j] for j in dropped)}" if dropped else ""))
+    if q.shape[1] == 0:
+        raise NLDSCParameterError(f'"{covar}": every covariate column is constant: nothing to adjust for')
+    return q
 
 
 # ---- the pairwise LD table (--pairs-out): one row per ordered pair (SNP_A, SNP_B) the run counts in WSA[SNP_A] ----
@@ -289,14 +318,18 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
                  verbose: int = 0, write_m: bool = False, flags: int = 0, device: int | None = None,
                  progress: bool | None = None, keep: str | None = None, remove: str | None = None,
                  annot: str | None = None, pairs_out: str | None = None, pairs_min_r2: float | None = None,
-                 pairs_budget: int = PAIRS_BUDGET):
-    """`pairs_out`: also write the pairwise LD table behind the scores there (write_pairs; `.gz` compresses), with
+                 pairs_budget: int = PAIRS_BUDGET, covar: str | None = None):
+    """`covar`: path of a PLINK covariate file (common.CovarFile): covariate-adjusted LD scores (cov-LDSC) on the
+    orthonormal basis of its columns for the run's individuals (covar_basis_of_run), in PLINK's sample order.
+    `pairs_out`: also write the pairwise LD table behind the scores there (write_pairs; `.gz` compresses), with
     `pairs_min_r2` only the pairs whose R2 or R2D exceeds it, in engine calls of at most `pairs_budget` pairs; the
     scores are the same, bit for bit.
     `keep` / `remove`: paths of `FID IID` lists (PLINK's / LDSC's --keep, --remove): the scores are computed on the
     .fam lines of the first minus those of the second, in PLINK's sample order (common.kept_individuals).
     `annot`: path of an LDSC `.annot` / `.annot.gz` file (common.AnnotFile): partitioned LD scores, the table gains
     L2_<name> and L2D_<name> columns and `write_m` also writes `<out>.M_annot`."""
+    if covar is not None:
+        reject_covar_options(annot, pairs_out)
     if pairs_out is not None:
         reject_pairs_options(annot)
     if annot is not None:
@@ -332,7 +365,14 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
     bar = Progress(bim_.n_snp, "SNPs", enabled=progress)
     bar.update(0, "reading the .bed and computing on the GPU", force=True)
     dist = _process_group()
-    if pairs_out is not None:  # the engine itself: one load, the sizing and emitting calls of every owned range
+    if covar is not None:  # the engine itself: the basis built once on the host, then one covariate run
+        from .genome import _default_runner
+        basis = covar_basis_of_run(covar, fam_, kept)
+        run = _default_runner(-1 if device is None else int(device), kept, fam_.n_org)
+        res, _ = run(bed_.data, bim_.n_snp, fam_.n_org, ld_wind_.data, maf_thr_.data, std_thr_.data, rsq_thr_.data,
+                     np.asarray(params.positions, dtype=np.float64), int(flags), covar=basis)
+        ld = _Result(res)
+    elif pairs_out is not None:  # the engine itself: one load, the sizing and emitting calls of every owned range
         from .genome import _default_runner
         run = _default_runner(-1 if device is None else int(device), kept, fam_.n_org)
         res, _ = run(bed_.data, bim_.n_snp, fam_.n_org, ld_wind_.data, maf_thr_.data, std_thr_.data, rsq_thr_.data,
