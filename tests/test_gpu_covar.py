@@ -21,7 +21,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REPO, load_set, record
+from conftest import GOLDEN, REPO, golden_sets, load_set, record
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -78,6 +78,22 @@ def dataset(name):
             args, N = (meta["ld_wind"], meta["maf"], meta["std_thr"], meta["rsq_thr"]), meta["n_org"]
         _sets[name] = (rows, pos, args, N, bed)
     return _sets[name]
+
+
+def register_set(name, rows, pos, args, N):
+    """A data set of another module (tests/test_gpu_covar_shapes.py) under `name`: dataset, vectors and cov_truth then
+    take it like the ones above."""
+    from nldsc_amd import synth
+    assert name not in golden_sets()
+    if name not in _sets:
+        _sets[name] = (rows, np.asarray(pos, np.float64), tuple(args), int(N), synth.bed_bytes(rows))
+    return _sets[name]
+
+
+def forget_set(name):
+    """Drops a registered set and its vectors (a set whose N-vectors take hundreds of megabytes)."""
+    _sets.pop(name, None)
+    _vec.pop(name, None)
 
 
 def load(engine, name):
@@ -206,19 +222,16 @@ def seven_covariates(name, seed=7):
 
 
 # ---- 1. projections -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("q", [1, 5, 17, 40, 64])  # 1, 1, 2, 3 and 4 groups of 16 covariates; across a chunk edge; the cap
-@pytest.mark.parametrize("name", ["n1000", "n1001", "n1002", "n1003", "allmiss", "n67", "n32773"])
-def test_projections(engines, name, q):
+def projection_bounds(name, Q):
+    """key -> (expected, bound) of Engine.covar_projections ("u", "w", "v", "wd") for the basis Q: the module
+    docstring's bound on U and W, propagated into v and w."""
     rows, pos, args, N, bed = dataset(name)
     A, R, st, (la, lr) = vectors(name)
-    Q = qr_basis(np.random.default_rng(100 + q).standard_normal((N, q)))
     U, W, v, gam, w = projections(A, R, Q, N)
     s = O.f64_setup(rows, N, args[0], args[1], args[2], pos, strict=True)
     live = s["passed"] & (st["counts"][:, [0, 2, 3]].sum(1) > 0)  # computed, not all-missing: the others report 0 / 1
     U, W = np.where(live[:, None], U, 0.0), np.where(live[:, None], W, 0.0)
     v, w = np.where(live, v, 1.0), np.where(live, w, 1.0)
-    if name == "allmiss":
-        assert (st["counts"][:, [0, 2, 3]].sum(1) == 0).any() and s["passed"][st["counts"][:, [0, 2, 3]].sum(1) == 0].any()
     absq = np.abs(Q).sum(0)
     bU = N * 2.0 ** -52 * absq[None, :] * 2 * np.abs(la).max(1)[:, None] + 8 * EPS * np.abs(U)
     bW = N * 2.0 ** -52 * absq[None, :] * 2 * np.abs(lr).max(1)[:, None] + 8 * EPS * np.abs(W)
@@ -226,17 +239,39 @@ def test_projections(engines, name, q):
     bv = 2 * ((2 * np.abs(U) + bU) * bU).sum(1) / N + 16 * EPS
     bw = 2 * ((np.abs(-2 * W + 2 * gam[:, None] * U) * bW + np.abs(2 * gam[:, None] * W - 2 * (gam ** 2)[:, None] * U) * bU)
               .sum(1) / N + ((bW * bW).sum(1) + (bU * bU).sum(1)) / N) / np.minimum(np.maximum(v, 1e-6), 1.0) + 64 * EPS
+    return {"u": (U, bU), "w": (W, bW), "v": (v, bv), "wd": (w, bw)}
+
+
+def assert_projections(p, bounds, label):
+    """Every array of p = Engine.covar_projections(q) finite and within its bound; key -> the worst error in units
+    of the bound."""
+    units = {}
+    for key, (exp, b) in bounds.items():
+        err = np.abs(p[key] - exp)
+        units[key] = float((err / np.maximum(b, 1e-300)).max())  # (b = 0 with err = 0: an all-missing SNP's zeros)
+        assert np.isfinite(p[key]).all() and (err <= b).all(), \
+            f"{label} {key}: worst {units[key]:.3g} x the bound at {np.argwhere(err > b)[:5]}"
+    return units
+
+
+@pytest.mark.parametrize("q", [1, 5, 17, 40, 64])  # 1, 1, 2, 3 and 4 groups of 16 covariates; across a chunk edge; the cap
+@pytest.mark.parametrize("name", ["n1000", "n1001", "n1002", "n1003", "allmiss", "n67", "n32773"])
+def test_projections(engines, name, q):
+    rows, pos, args, N, bed = dataset(name)
+    A, R, st, (la, lr) = vectors(name)
+    Q = qr_basis(np.random.default_rng(100 + q).standard_normal((N, q)))
+    bounds = projection_bounds(name, Q)
+    bU, bW = bounds["u"][1], bounds["w"][1]
+    if name == "allmiss":
+        s = O.f64_setup(rows, N, args[0], args[1], args[2], pos, strict=True)
+        assert (st["counts"][:, [0, 2, 3]].sum(1) == 0).any() and s["passed"][st["counts"][:, [0, 2, 3]].sum(1) == 0].any()
     rec, got = {}, {}
     for orient, e in engines.items():
         load(e, name)
         e.run(*args, pos, covar=Q)
         p = got[orient] = e.covar_projections(q)
-        for key, exp, b in (("u", U, bU), ("w", W, bW), ("v", v, bv), ("wd", w, bw)):
-            err = np.abs(p[key] - exp)
-            units = float((err / np.maximum(b, 1e-300)).max())  # (b = 0 with err = 0: an all-missing SNP's zeros)
+        for key, units in assert_projections(p, bounds, f"{name} q={q} orient={orient}").items():
             rec[f"{key} orient {orient}"] = units
-            assert np.isfinite(p[key]).all() and (err <= b).all(), \
-                f"{name} q={q} orient={orient} {key}: worst {units:.3g} x the bound at {np.argwhere(err > b)[:5]}"
         if name == "allmiss":
             dead = st["counts"][:, [0, 2, 3]].sum(1) == 0
             assert (p["u"][dead] == 0).all() and (p["w"][dead] == 0).all()
