@@ -2909,24 +2909,42 @@ __global__ void __launch_bounds__(64, 2) band_f4_epi_kernel(const SnpConst* __re
 // item's 64 slots are staged through LDS, each column's four weighted sums reduced with reduce_rows4 / xlane in the
 // plain epilogue's order and added to category-major fixed-point accumulators acc[c * n_snp + g] in units of
 // 1 / ascale[c] (= 2^(-44 + e_c), band_plan.h annot_scale_exp: a SNP's total stays below 2^63 for |a| <= 2^e_c) with
-// 64-bit integer atomics: order-independent, bit-reproducible.  What that rounding drops of an item's partial goes,
-// in units of 2^-40 of the first, to a second accumulator of the same layout (|residual| <= 2^39 per item, fewer
-// than 2^20 items per SNP), so a total carries the fp64 partials' own precision: a column and a multiple of it then
-// agree to the rounding of their fp64 products, whatever e_c.
+// 64-bit integer atomics: order-independent, bit-reproducible.  What that rounding drops goes, in units of 2^-40 of
+// the first, to a second accumulator of the same layout (|residual| < 2^40 per item, fewer than 2^20 items per SNP).
+// The split is made per term, before any sum (annot_term): the product a r2 exactly (its fp64 rounding error from an
+// FMA) as an integer of the first unit plus an integer of the second, both held in doubles, so that every sum of
+// an item — in the lane, across lanes — is a sum of integers below 2^53 and exact.  A total is then the sum of its
+// terms to 2^-85+e_c each, however much they cancel: a column and a multiple of it agree to the rounding of the
+// multiple's own weights (a sum of 151 terms of magnitude 1.69 that cancel to 4e-5 missed a relative 1e-12 against its
+// x1000 column while the products and the 32-term partials were rounded in fp64).
 constexpr int ANNOT_CHUNK = 16;
 constexpr double ANNOT_LO_SCALE = 1099511627776.0;  // 2^40
+constexpr double ANNOT_ROUND = 6755399441055744.0;  // 1.5 x 2^52: (x + this) - this = x rounded to an integer, |x| < 2^51
 
-// One slot's weighted sum of one work item and one annotation -> that annotation's per-SNP total.  Exact zeros (an
-// annotation without a member among the other block's SNPs: binary annotations are mostly zero) add nothing; a
-// non-finite sum (a window poisoned by an all-missing SNP: 0 * NaN is NaN too) never reaches the integer conversion —
-// the plain sums of the same slot set the nanf bit finalize reads for every annotation.
-__device__ __forceinline__ void flush_annot(int g, double v, double scale, int own_lo, int own_hi, int n_snp,
+// One term a * p of an annotation sum in units of 1 / scale (a power of two; |a p scale| <= ~2^44): hi its nearest
+// integer, lo the rest — the exact remainder plus the product's own rounding error — in units of 2^-40, rounded.
+// A non-finite p gives non-finite parts.
+__device__ __forceinline__ void annot_term(double p, double a, double scale, double& hi, double& lo) {
+    const double v = p * a, e = fma(p, a, -v);
+    const double s = v * scale;
+    hi = (s + ANNOT_ROUND) - ANNOT_ROUND;
+    lo = (((s - hi) + e * scale) * ANNOT_LO_SCALE + ANNOT_ROUND) - ANNOT_ROUND;  // (s - hi is exact, <= 1/2)
+}
+
+// One slot's weighted sum of one work item and one annotation (annot_term's two parts, summed: integers) -> that
+// annotation's per-SNP total.  Exact zeros (an annotation without a member among the other block's SNPs: binary
+// annotations are mostly zero) add nothing; a non-finite sum (a window poisoned by an all-missing SNP: 0 * NaN is NaN
+// too) never reaches the integer conversion — the plain sums of the same slot set the nanf bit finalize reads for
+// every annotation.
+__device__ __forceinline__ void flush_annot(int g, double v_hi, double v_lo, int own_lo, int own_hi, int n_snp,
                                             double* acc, double* acc_lo) {
-    if (v == 0.0 || !isfinite(v) || g < own_lo || g >= own_hi || g >= n_snp) return;
-    const double s = v * scale;  // (a power of two: exact)
-    const long long hi = __double2ll_rn(s);
-    const long long lo = __double2ll_rn((s - (double)hi) * ANNOT_LO_SCALE);  // (the difference is exact, <= 1/2)
-    atomicAdd(reinterpret_cast<unsigned long long*>(&acc[g]), (unsigned long long)hi);
+    if ((v_hi == 0.0 && v_lo == 0.0) || !isfinite(v_hi) || !isfinite(v_lo) || g < own_lo || g >= own_hi || g >= n_snp)
+        return;
+    long long hi = (long long)v_hi, lo = (long long)v_lo;  // (|hi| < 2^51, |lo| < 2^47)
+    const long long carry = lo >> 40;                      // (floor: 0 <= lo - carry 2^40 < 2^40)
+    hi += carry;
+    lo -= carry * (1ll << 40);
+    if (hi != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&acc[g]), (unsigned long long)hi);
     if (lo != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&acc_lo[g]), (unsigned long long)lo);
 }
 
@@ -3000,28 +3018,39 @@ __global__ void __launch_bounds__(64) band_f4_epi_annot_kernel(
             const size_t cbase = (size_t)(c0 + cc) * n_snp;
             const double scale = ascale[c0 + cc];
             const double aj = wt[cc][sj];
-            SlotSum col = {0.0, 0.0, 0}, mine = {0.0, 0.0, 0};
+            // (the sums of annot_term's first parts, and — `lo` — of its second parts: integers, every sum exact)
+            SlotSum col = {0.0, 0.0, 0}, mine = {0.0, 0.0, 0}, col_lo = {0.0, 0.0, 0}, mine_lo = {0.0, 0.0, 0};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                SlotSum rowv[4];
+                SlotSum rowv[4], rowl[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int r = 4 * q + k;
                     const double ai = wt[cc][k + 8 * q + 4 * h];
-                    rowv[k] = SlotSum{pv[0][r][lane] * aj, DOM ? pv[2][r][lane] * aj : 0.0, 0};
-                    col.l2 += pv[1][r][lane] * ai;
-                    if (DOM) col.l2d += pv[3][r][lane] * ai;
+                    double th, tl;
+                    rowv[k] = rowl[k] = SlotSum{0.0, 0.0, 0};
+                    annot_term(pv[0][r][lane], aj, scale, rowv[k].l2, rowl[k].l2);
+                    if (DOM) annot_term(pv[2][r][lane], aj, scale, rowv[k].l2d, rowl[k].l2d);
+                    annot_term(pv[1][r][lane], ai, scale, th, tl);
+                    col.l2 += th;
+                    col_lo.l2 += tl;
+                    if (DOM) {
+                        annot_term(pv[3][r][lane], ai, scale, th, tl);
+                        col.l2d += th;
+                        col_lo.l2d += tl;
+                    }
                 }
-                const SlotSum t = reduce_rows4(rowv, i);
-                if (my_q == q) mine = t;
+                const SlotSum t = reduce_rows4(rowv, i), t_lo = reduce_rows4(rowl, i);
+                if (my_q == q) mine = t, mine_lo = t_lo;
             }
             col = col + xlane<32>(col);
-            flush_annot(g_row, mine.l2, scale, own_lo, own_hi, n_snp, l2c_acc + cbase, l2c_lo + cbase);
-            if (h == 0) flush_annot(cj.g, col.l2, scale, own_lo, own_hi, n_snp, l2c_acc + cbase, l2c_lo + cbase);
+            col_lo = col_lo + xlane<32>(col_lo);
+            flush_annot(g_row, mine.l2, mine_lo.l2, own_lo, own_hi, n_snp, l2c_acc + cbase, l2c_lo + cbase);
+            if (h == 0) flush_annot(cj.g, col.l2, col_lo.l2, own_lo, own_hi, n_snp, l2c_acc + cbase, l2c_lo + cbase);
             if (DOM) {
-                flush_annot(g_row, mine.l2d, scale, own_lo, own_hi, n_snp, l2dc_acc + cbase, l2dc_lo + cbase);
+                flush_annot(g_row, mine.l2d, mine_lo.l2d, own_lo, own_hi, n_snp, l2dc_acc + cbase, l2dc_lo + cbase);
                 if (h == 0)
-                    flush_annot(cj.g, col.l2d, scale, own_lo, own_hi, n_snp, l2dc_acc + cbase, l2dc_lo + cbase);
+                    flush_annot(cj.g, col.l2d, col_lo.l2d, own_lo, own_hi, n_snp, l2dc_acc + cbase, l2dc_lo + cbase);
             }
         }
     }

@@ -76,11 +76,13 @@ def six_columns(M, seed=21):
                      1000.0 * z, np.zeros(M)], axis=1)
 
 
-def truth(rows, N, args, pos, annot, strict=False):
-    """(L2[j, c], L2D[j, c]) from the exact per-pair r2adj; NaN rows for SNPs that are not computed."""
+def truth(rows, N, args, pos, annot, strict=False, targets=None):
+    """(L2[j, c], L2D[j, c]) from the exact per-pair r2adj; NaN rows for SNPs that are not computed (and, with
+    `targets`, for every SNP that is none of them)."""
     M, C = annot.shape
     l2, l2d = np.full((M, C), np.nan), np.full((M, C), np.nan)
-    for j, p in enumerate(O.pair_r2_f64(rows, N, args[0], args[1], args[2], pos, np.arange(M), strict=strict)):
+    targets = np.arange(M) if targets is None else np.asarray(targets)
+    for j, p in zip(targets, O.pair_r2_f64(rows, N, args[0], args[1], args[2], pos, targets, strict=strict)):
         if p is None:
             continue
         ks, r2a, kds, r2d = p
@@ -174,9 +176,10 @@ def test_consistent_with_the_plain_score(plain_and_annot, name):
 def test_times_1000_column(plain_and_annot):
     """3 (last item). the x1000 column equals 1000 x its base column within relative 1e-12, taken per value:
     |V - 1000 b| <= 1e-12 |1000 b|.  The two columns accumulate at different fixed-point scales (2^-42 and 2^-32 for a
-    standard normal column); what each item's partial loses to that rounding goes to the residual accumulators, so
-    the totals carry the fp64 partials' precision.  In exact arithmetic on these inputs (1000 z is itself rounded)
-    the worst relative gap is 9.4e-14; measured on the MI355X: 3.0e-13."""
+    standard normal column); every term a r2 is split exactly into a part at that scale and a residual part before
+    any sum (annot_term), so the totals are the sums of their terms.  In exact arithmetic on these inputs (1000 z is
+    itself rounded) the worst relative gap is 9.4e-14; measured on the MI355X: 9.2e-14 (3.0e-13 while the products and
+    an item's partial sums were rounded in fp64)."""
     bad, rec = [], {}
     for name in SETS:
         plain, got, annot = plain_and_annot(name)

@@ -287,6 +287,21 @@ def clear_threshold(values, lo=0.04, hi=0.06, gap=1e-6, centre=0.05):
     return min(cand, key=lambda c: abs(c - centre)) if cand else None
 
 
+def filtered_truth(truth, thr):
+    """signed_truth's rows with the entries whose exact r2adj(r) or r2adj(rd) exceeds thr."""
+    kept = []
+    for p in truth:
+        if p is None:
+            kept.append(None)
+            continue
+        ks, r, r2a, kd, rd, r2d = p
+        d_over = np.zeros(len(ks), bool)
+        d_over[kd] = r2d > thr
+        m = (r2a > thr) | d_over
+        kept.append((ks[m], r[m], r2a[m], kd[m], rd[m[kd]], r2d[m[kd]]))
+    return kept
+
+
 def test_filter(engine, truth_n1001):
     """8. min_r2 near 0.05, clear by 1e-6 of every pair's exact values: the filtered table is the truth's filtered
     pair set exactly, values within the bar."""
@@ -297,16 +312,7 @@ def test_filter(engine, truth_n1001):
     assert np.abs(allv[np.isfinite(allv)] - thr).min() >= 1e-6
     pos, args = load(engine, "n1001")
     t = engine.run_pairs(*args, pos, flags=EXACT_RARE, min_r2=thr)
-    kept = []
-    for p in truth_n1001:
-        if p is None:
-            kept.append(None)
-            continue
-        ks, r, r2a, kd, rd, r2d = p
-        d_over = np.zeros(len(ks), bool)
-        d_over[kd] = r2d > thr
-        m = (r2a > thr) | d_over
-        kept.append((ks[m], r[m], r2a[m], kd[m], rd[m[kd]], r2d[m[kd]]))
+    kept = filtered_truth(truth_n1001, thr)
     n_kept = sum(len(p[0]) for p in kept if p is not None)
     assert 0 < n_kept < len(allv) and t["n_pairs"] == n_kept
     w = check_rows(t, kept, N, np.arange(len(rows)))
@@ -327,13 +333,18 @@ def short_rows(M, seed):
     return rows, synth.bed_bytes(rows)
 
 
-def test_full_window(engine):
-    """9a. M = 32 * 9 + 1 and a window as long as the chromosome: every block pair is an item, the last block holds
-    one SNP, and row j is exactly the passed SNPs other than j."""
+def full_window_set():
+    """(M, rows, bed bytes, positions, arguments): M = 32 * 9 + 1 short rows and a window as long as the chromosome."""
     M = 32 * 9 + 1
     rows, bed = short_rows(M, 501)
     pos = np.cumsum(np.random.default_rng(5).integers(0, 600, size=M)).astype(np.float64)
-    args = (float(pos[-1]), MAF67, STD67, RSQ67)
+    return M, rows, bed, pos, (float(pos[-1]), MAF67, STD67, RSQ67)
+
+
+def test_full_window(engine):
+    """9a. M = 32 * 9 + 1 and a window as long as the chromosome: every block pair is an item, the last block holds
+    one SNP, and row j is exactly the passed SNPs other than j."""
+    M, rows, bed, pos, args = full_window_set()
     engine.set_keep(None)
     engine.load_bed_bytes(bed, M, N67)
     t = engine.run_pairs(*args, pos, flags=EXACT_RARE)
@@ -345,9 +356,9 @@ def test_full_window(engine):
     assert_plain_bitwise(t, engine.run(*args, pos, flags=EXACT_RARE), "full window")
 
 
-def test_ragged(engine):
-    """9b. ~3 000 ragged positions: 230 SNPs at one position, a gap beyond the window, exact window ties.  Row lengths
-    equal the run's l2_ws; the rows of ~60 targets (block edges, the tie run, the ends) equal the truth's."""
+def ragged_set():
+    """(M, rows, bed bytes, positions, arguments, the run of SNPs at one position, the exact window ties): ~3 000
+    ragged positions, 230 SNPs at one position, a gap beyond the window, exact window ties."""
     M, w = 3001, 3000.0
     rng = np.random.default_rng(77)
     gaps = np.round(rng.exponential(30.0, size=M))
@@ -364,6 +375,23 @@ def test_ragged(engine):
     assert (np.diff(pos) >= 0).all()
     rows, bed = short_rows(M, 502)
     args = (w, MAF67, STD67, RSQ67)
+    return M, rows, bed, pos, args, run, ties
+
+
+def ragged_targets(M, run, ties):
+    """~60 targets: block edges, the tie run, the exact window ties, the ends, 30 random SNPs."""
+    tg = {0, 1, 31, 32, 33, M - 1, M - 2, 32 * 40 - 1, 32 * 40, 32 * 40 + 1, run[0] - 1, run[0], (run[0] + run[1]) // 2,
+          run[1] - 1, run[1], 32 * 93, 32 * 93 + 31, 959, 991, 992, 1023, 1024}
+    tg |= {x for ab in ties for x in ab} | {x + d for ab in ties for x in ab for d in (-1, 1)}
+    tg |= set(np.random.default_rng(M).choice(M, 30, replace=False).tolist())
+    tg = np.array(sorted(x for x in tg if 0 <= x < M))
+    return tg
+
+
+def test_ragged(engine):
+    """9b. ~3 000 ragged positions: 230 SNPs at one position, a gap beyond the window, exact window ties.  Row lengths
+    equal the run's l2_ws; the rows of ~60 targets (block edges, the tie run, the ends) equal the truth's."""
+    M, rows, bed, pos, args, run, ties = ragged_set()
     engine.set_keep(None)
     engine.load_bed_bytes(bed, M, N67)
     # (FLAG_EXACT_RARE: at N = 67 nearly every SNP is a rare variant, and the truth is the exact restatement)
@@ -373,11 +401,7 @@ def test_ragged(engine):
     computed = plain["l2_ws"] >= 0
     lens = np.diff(t["row_ptr"])
     assert np.array_equal(lens[computed], plain["l2_ws"][computed]) and not lens[~computed].any()
-    tg = {0, 1, 31, 32, 33, M - 1, M - 2, 32 * 40 - 1, 32 * 40, 32 * 40 + 1, run[0] - 1, run[0], (run[0] + run[1]) // 2,
-          run[1] - 1, run[1], 32 * 93, 32 * 93 + 31, 959, 991, 992, 1023, 1024}
-    tg |= {x for ab in ties for x in ab} | {x + d for ab in ties for x in ab for d in (-1, 1)}
-    tg |= set(np.random.default_rng(M).choice(M, 30, replace=False).tolist())
-    tg = np.array(sorted(x for x in tg if 0 <= x < M))
+    tg = ragged_targets(M, run, ties)
     assert len(tg) >= 55
     truth = signed_truth(rows, N67, args, pos, bed=bed, targets=tg)
     assert sum(p is not None for p in truth) >= 40
