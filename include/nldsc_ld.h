@@ -112,6 +112,15 @@ void nldsc_engine_destroy(nldsc_engine* e);
  *   t2           super-item kernels for missing-free blocks: 0 none, 1 2x2 routed, 2 2x2 for all, [3] 4x4 quad
  *   band_rounds  [1] single-block fp4 band in launches of one round of wave slots; 0 one launch
  *   f4_nc2       [1] additive-only fp4 items of two column blocks; 0 single block pairs
+ *   f4_nc2_dom   [1] add+dom fp4 bands of long unsegmented rows (2^17 <= n_org < 2^19, GPU plan, band_rounds 1):
+ *                pairs of neighbouring column blocks (32x64 tiles) at one wave per SIMD, in whole
+ *                rounds of 4 items per CU from two such rounds on; the pairs past the last full round and the rows' odd
+ *                blocks run as single block pairs (rounds of the single-block kernel, the partial last one K-split).
+ *                With super-item routing the pairs and singles no super-item kernel takes whole are compacted first, and
+ *                a pair runs with the one block the routing leaves it.
+ *                0 single block pairs.  Plain runs only: annotated, pairs and covariate runs keep their batches
+ *   colpair_round_items [0] tests: pair items per round of f4_nc2_dom (0: 4 per CU), then from one round on and on
+ *                rows of any unsegmented length
  *   q_rounds     [1] quad super-items in launches of one workgroup per CU; 0 one launch
  *   defer_rep    [1] K loops of items holding a replayed rare variant in the main launch; 0 a later KC launch
  *   annot_batch_items [0] annotated runs: block-pair items per batch (0: what the Gram scratch cap holds)
@@ -294,7 +303,10 @@ int nldsc_engine_run_device_finish(nldsc_engine* e, const int64_t* import_dev, i
  * Also: algorithmic FLOPs (2N(1/2 sum WSA + sum WSD)), FLOPs issued to the matrix cores by the
  * band kernels (counted on the GPU per work item as each kernel decides them: the products of missing-free blocks
  * and the transposed products of diagonal blocks that are skipped are not counted; padded sample slots are), SNP
- * pairs (sum WSA) of the last run, and the band kernel's work-item count. */
+ * pairs (sum WSA) of the last run, and the band kernel's work-item count (block pairs, also when column-block pair
+ * items ran).  With f4_nc2_dom the count is that of the single-block plan, so it does not depend on the option: a
+ * pair item whose two column blocks differ in missingness runs the loop of their union and issues the missing-call
+ * products for the missing-free block as well (on all-zero operands), which the count leaves out. */
 int nldsc_engine_timings(const nldsc_engine* e, double* ms6, double* flop_alg, double* flop_issued,
                          double* pairs, int32_t* n_band_items);
 /* Path of the last run: 2 = exact Gram on fp4 MFMAs, 1 = exact Gram on int8 MFMAs, 0 = fp32;
@@ -324,6 +336,10 @@ int nldsc_engine_band_tail_ksplit(const nldsc_engine* e);
 #define NLDSC_BAND_F4_ROUTED 6
 #define NLDSC_BAND_F4_QUAD 7 /* option t2 = 3: missing-free 4x4 super-items in the quad workgroups (64x64 tiles per
                                 wave), the rest in the single-block kernel */
+#define NLDSC_BAND_F4_COLPAIR 8 /* option f4_nc2_dom: add+dom bands of long rows, pairs of neighbouring column blocks
+                                   (32x64 tiles) at one wave per SIMD in whole rounds, the rest in the single-block
+                                   kernel; nldsc_engine_band_round_items then counts the block pairs of a pair
+                                   round (two per pair item: 8 per CU), the unit of the work-item count */
 int nldsc_engine_band_kernel(const nldsc_engine* e);
 /* Where the last host-result run (nldsc_engine_run) wrote its owned slice: 1 straight into the caller's arrays (all
  * seven in nldsc_host_alloc buffers, zero copy), 0 through the engine's landing buffer and host copies, -1 no host

@@ -221,6 +221,26 @@ SingleShape shape_single(int n_single, int n_it, int n_cu, bool use_f4, int kspl
     return s;
 }
 
+ColpairShape shape_colpair(int n_pairs, int n_singles, int n_it, int n_cu, int round_override, bool ksplit_ok,
+                           bool defer_wanted, size_t rep_gram_max_slots) {
+    ColpairShape c = {};
+    const int round = round_override > 0 ? round_override : 4 * n_cu;
+    const int min_rounds = round_override > 0 ? 1 : COLPAIR_ROUND_MIN;
+    if (n_pairs < 0 || n_singles < 0 || n_it > F4_SEG_CHUNKS || (int64_t)n_pairs < (int64_t)min_rounds * round)
+        return c;
+    c.round_items = round;
+    c.n_pair_full = n_pairs / round * round;
+    c.n_rest = n_singles + 2 * (n_pairs - c.n_pair_full);
+    // the rest continues the band: rounds of the two-wave kernel (twice the slots), the partial last one K-split
+    SingleShape& r = c.rest;
+    r.round_items = 2 * round;
+    const int tail = c.n_rest % r.round_items;
+    r.tail_p = tail > 0 ? choose_ksplit(tail, n_it, n_cu, ksplit_ok) : 1;
+    r.n_full = r.tail_p > 1 ? c.n_rest - tail : c.n_rest;
+    r.defer = defer_wanted && (size_t)c.n_pair_full * 2 + (size_t)r.n_full <= rep_gram_max_slots;
+    return c;
+}
+
 int annot_scale_exp(double max_abs) {
     if (!(max_abs > 0.0) || !std::isfinite(max_abs)) return 0;
     int k = 0;
@@ -270,7 +290,8 @@ std::vector<int32_t> pairs_split_ranges(const int64_t* row_ptr, int32_t n, int64
     return ends;
 }
 
-int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it) {
+int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it, bool colpair) {
+    if (colpair) return NLDSC_BAND_F4_COLPAIR;
     if (use_t2) return t2_mode == 3 ? NLDSC_BAND_F4_QUAD : t2_mode == 1 ? NLDSC_BAND_F4_ROUTED : NLDSC_BAND_F4_2X2;
     if (path != 2) return path != 0 ? NLDSC_BAND_I8 : NLDSC_BAND_F32;
     return ksplit > 1 ? NLDSC_BAND_F4_KSPLIT : n_it > F4_SEG_CHUNKS ? NLDSC_BAND_F4_SEG : NLDSC_BAND_F4;

@@ -43,6 +43,19 @@ BandChoice choose_band(int n_items, int n_it, int n_cu, bool use_f4, bool ksplit
 struct SingleShape { int round_items, tail_p, n_full; bool defer; };
 SingleShape shape_single(int n_single, int n_it, int n_cu, bool use_f4, int ksplit, bool band_rounds, bool nc2,
                          bool ksplit_ok, bool defer_wanted, size_t rep_gram_max_slots);
+// ---- add+dom column-pair rounds (option "f4_nc2_dom"): the one-wave 32 x 64 kernel takes the plan's (I, J, 2) pairs
+// in whole rounds of one item per SIMD (4 per CU); everything else — the pairs past the last full round, back as two
+// single-block items each, and the odd runs' leftover singles — is a single-block list that goes on in rounds of the
+// two-wave kernel with its partial last round K-split, as the tail of a single-block band does.
+// Pair rounds only from COLPAIR_ROUND_MIN full rounds on: below that the band is a shard's 1-2 rounds, whose launches
+// stay what they are (one pair round of 2 048 block pairs is one round of the two-wave kernel).
+constexpr int COLPAIR_ROUND_MIN = 2;
+// round_items 0: no pair rounds (the single-block plan runs as it is).  Else pairs [0, n_pair_full) go in launches of
+// round_items, and `rest` shapes the n_rest single-block items; defer: as SingleShape's, over both kernels' slots.
+// round_override > 0 (option "colpair_round_items", tests): that many pairs per round, from one round on.
+struct ColpairShape { int round_items, n_pair_full, n_rest; SingleShape rest; };
+ColpairShape shape_colpair(int n_pairs, int n_singles, int n_it, int n_cu, int round_override, bool ksplit_ok,
+                           bool defer_wanted, size_t rep_gram_max_slots);
 // ---- annotated runs (nldsc_engine_run_annot): fixed-point scale and batches ----
 // Exponent e_c of an annotation column's fixed-point scale 2^(-44 + e_c): max(0, ceil(log2(max_abs))) for the
 // column's largest |a| (finite, >= 0), so |a| <= 2^e_c and a SNP's weighted total (< 2^19 * 2^e_c) fits 63 bits; a
@@ -89,6 +102,6 @@ constexpr int64_t PAIRS_MAX_CELLS = (int64_t)1 << 27;
 std::vector<int32_t> pairs_split_ranges(const int64_t* row_ptr, int32_t n, int64_t budget);
 
 // NLDSC_BAND_* (nldsc_ld.h) of a run; path: 0 fp32, 1 int8, 2 fp4; t2_mode: option "t2"
-int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it);
+int band_kernel_code(bool use_t2, int t2_mode, int path, int ksplit, int n_it, bool colpair = false);
 
 }  // namespace nldsc

@@ -357,6 +357,15 @@ struct nldsc_engine {
     // additive-only fp4 band in 32 x 64 tiles (column-block pair items, the row strip decoded once for two column
     // blocks; option "f4_nc2" 0 turns it off): C2 band 2.85 -> 2.78 ms, one engine per process (r03_c2_nc2.json)
     bool f4_nc2 = true;
+    // add+dom fp4 band of long unsegmented rows in 32 x 64 tiles at one wave per SIMD (column-block pair items in
+    // rounds of 4 per CU, nldsc::shape_colpair; option "f4_nc2_dom" 0 turns it off), the rest of the band in the
+    // single-block kernel.  colpair_round_items (option, tests): pairs per round, also on short rows
+    bool f4_nc2_dom = true;
+    int colpair_round_items = 0;
+    DevBuf<int4> items_p, items_s;   // the column-pair plan: pairs; leftover singles, then the last pairs' blocks
+    DevBuf<int4> items_pu, items_su; // routed runs: the same lists without the items the super-item kernel takes whole
+    DevBuf<int> compact_tmp2;        // (their chunk counts and totals; the totals land in h_meta[10..11])
+    DevBuf<int> plan_counts_p, plan_counts_s;
     // single-block fp4 band in launches of one round of wave slots (option "band_rounds" 0: one launch)
     bool band_rounds = true;
     DevBuf<uint8_t> blk_miss;
@@ -610,6 +619,8 @@ int nldsc_engine_set_option(nldsc_engine* e, const char* name, int64_t value, ch
         {"t2", 0, 3, [&](int64_t v) { e->t2_mode = (int)v; }},
         {"band_rounds", 0, 1, [&](int64_t v) { e->band_rounds = v != 0; }},
         {"f4_nc2", 0, 1, [&](int64_t v) { e->f4_nc2 = v != 0; }},
+        {"f4_nc2_dom", 0, 1, [&](int64_t v) { e->f4_nc2_dom = v != 0; }},
+        {"colpair_round_items", 0, 1 << 20, [&](int64_t v) { e->colpair_round_items = (int)v; }},
         {"q_rounds", 0, 1, [&](int64_t v) { e->q_rounds = v != 0; }},
         {"defer_rep", 0, 1, [&](int64_t v) { e->defer_rep = v != 0; }},
         {"annot_batch_items", 0, INT32_MAX, [&](int64_t v) { e->annot_batch_items = (int)v; }},
@@ -939,7 +950,7 @@ RunShape run_shape(const nldsc_engine* e, const nldsc_ld_params* p, int own_begi
 
 // How the band is scheduled: what the positions and the engine's options decide on top of the shape.
 struct PlanMode {
-    bool sorted, gpu_plan, fused, t2_cand, nc2, routed, quad;
+    bool sorted, gpu_plan, fused, t2_cand, nc2, nc2d, routed, quad;
     int route_shift;  // super-items of 2^route_shift blocks a side
 };
 
@@ -960,8 +971,12 @@ PlanMode plan_mode(const nldsc_engine* e, const nldsc_ld_params* p, const RunSha
     // additive-only fp4 items of two column blocks (GPU plan, unsegmented rows; no K-split: its partial kernel takes
     // single block pairs)
     m.nc2 = e->f4_nc2 && m.gpu_plan && s.use_f4 && !s.dom && s.n_it <= nldsc::F4_SEG_CHUNKS;
+    // add+dom column-pair rounds beside the single-block plan: long unsegmented rows in round launches (or any
+    // unsegmented rows with the tests' round size); plain runs only (enqueue_band)
+    m.nc2d = e->f4_nc2_dom && m.gpu_plan && s.use_f4 && s.dom && s.n_it <= nldsc::F4_SEG_CHUNKS && e->band_rounds &&
+             (s.n_it >= 1024 || e->colpair_round_items > 0);
     // annotated runs: single-block items only, whatever the options say (enqueue_band_annot)
-    if (annot) m.t2_cand = m.nc2 = false;
+    if (annot) m.t2_cand = m.nc2 = m.nc2d = false;
     m.routed = e->t2_mode == 1 || e->t2_mode == 3;
     m.quad = e->t2_mode == 3;
     m.route_shift = m.quad ? 2 : 1;
@@ -1180,8 +1195,12 @@ int ensure_run_buffers(nldsc_engine* e, const RunShape& s, const PlanMode& m, ch
         HIPCHK(e->Aw.ensure(2 * M + (M + 255) / 256));
         HIPCHK(e->plan_rows.ensure((size_t)s.nblk));
         HIPCHK(e->plan_counts.ensure(n_t * n_t));
-        HIPCHK(e->plan_meta.ensure(8));  // [0, 4) single-block plan, [4, 8) super-item plan
-        HIPCHK(e->h_meta.ensure(8 * sizeof(int)));
+        HIPCHK(e->plan_meta.ensure(12));  // [0, 4) single-block plan, [4, 8) super-item plan, [8, 10) column-pair plan
+        HIPCHK(e->h_meta.ensure(12 * sizeof(int)));
+        if (m.nc2d) {
+            HIPCHK(e->plan_counts_p.ensure(n_t * n_t));
+            HIPCHK(e->plan_counts_s.ensure(n_t * n_t));
+        }
         if (m.fused) HIPCHK(e->items.ensure(nldsc::plan_small_items(s.M)));  // (emitted with the plan)
         if (m.t2_cand) {
             const size_t nblk2 = (size_t)(s.nblk + 1) / 2, n_t2 = (nblk2 + 15) / 16;
@@ -1283,6 +1302,7 @@ struct Schedule {
     int ksplit = 1;                 // K-split of the whole band
     bool use_t2 = false;            // the super-item kernels run
     bool compact = false;           // the single-block kernel's items are compacted (items_u, count in h_route)
+    bool colpair = false;           // the add+dom column-pair plan is queued (items_p / items_s, counts in h_meta[8..9])
 };
 
 // The GPU plan: the host waits for its two counters, decides the kernels, and queues the work lists on the plan stream.
@@ -1315,6 +1335,26 @@ int schedule_on_gpu(nldsc_engine* e, const RunShape& s, const PlanMode& m, Sched
         if (sc.n_items > 0 && !m.fused)
             HIPCHK(nldsc::launch_plan_emit(s.M, e->plan_rows.p, e->plan_meta.p, e->plan_counts.p, e->items.p, ps,
                                            m.nc2));
+    }
+    // add+dom column-pair rounds: the pairs and leftover singles of the same rows, beside the single-block list (which
+    // stays the run's item count and its issued-product count); their totals reach the host before the band
+    // (h_meta[8..9]; routed runs compact both lists in enqueue_band, counts in h_meta[10..11])
+    {
+        const int round = e->colpair_round_items > 0 ? e->colpair_round_items : 4 * e->n_cu;
+        const int min_rounds = e->colpair_round_items > 0 ? 1 : nldsc::COLPAIR_ROUND_MIN;
+        // (with the super-item kernels: only beside routing, which leaves the single-block kernels the rest)
+        sc.colpair = m.nc2d && (!sc.use_t2 || m.routed) && (sc.ksplit == 1 || e->colpair_round_items > 0) &&
+                     (int64_t)sc.n_items >= (int64_t)2 * min_rounds * round;
+    }
+    if (sc.colpair) {
+        HIPCHK(e->items_p.ensure((size_t)sc.n_items));
+        HIPCHK(e->items_s.ensure((size_t)sc.n_items));
+        volatile int* tot = reinterpret_cast<volatile int*>(e->h_meta.p) + 8;
+        tot[0] = tot[1] = -1;  // (the copy below lands the counts, >= 0)
+        HIPCHK(nldsc::launch_plan_split(s.M, e->plan_rows.p, e->plan_meta.p, e->plan_counts_p.p, e->plan_counts_s.p,
+                                        e->plan_meta.p + 8, e->items_p.p, e->items_s.p, ps));
+        HIPCHK(hipMemcpyAsync(e->h_meta.p + 8 * sizeof(int), e->plan_meta.p + 8, 2 * sizeof(int), hipMemcpyDeviceToHost,
+                              ps));
     }
     sc.compact = sc.use_t2 && m.routed && sc.n_items > 0;
     if (sc.compact) {
@@ -1432,6 +1472,24 @@ hipError_t launch_single(nldsc_engine* e, const nldsc::BandArgs& a, const RunSha
         r = nldsc::launch_band_f4_deferred_epi(a, n_full * per, rep);
     if (r != hipSuccess || n_full == L.n) return r;
     return nldsc::launch_band_f4_split(a, L.shape.tail_p, L.items + n_full, L.n - n_full, e->gram.p, which, L.miss);
+}
+
+// Column-pair rounds (nldsc::shape_colpair): the pairs' full rounds in the one-wave kernel, then the rest as a
+// single-block band; the deferred rare-variant items of both share the slot tables, their epilogues after the replay
+// (pairs / rest: the lists, compacted in routed runs; miss: the routing map then — a pair may keep one block, and the
+// last pairs' single blocks are not compacted)
+hipError_t launch_colpair(nldsc_engine* e, const nldsc::BandArgs& a, const nldsc::ColpairShape& cp, const int4* pairs,
+                          const int4* rest, const uint8_t* miss, int which) {
+    const nldsc::SingleShape& rs = cp.rest;
+    const bool dfr = rs.defer;
+    const nldsc::DeferredEpi rep = {e->rep_gram.p, e->rep_items.p, e->rep_count.p};
+    hipError_t r = nldsc::launch_band_f4(a, 2, pairs, cp.n_pair_full, which, miss, cp.round_items, dfr ? &rep : nullptr);
+    if (r == hipSuccess)
+        r = nldsc::launch_band_f4(a, 1, rest, rs.n_full, which, miss, rs.round_items, dfr ? &rep : nullptr);
+    if (r == hipSuccess && dfr && (which & 2))
+        r = nldsc::launch_band_f4_deferred_epi(a, 2 * cp.n_pair_full + rs.n_full, rep);
+    if (r != hipSuccess || rs.n_full == cp.n_rest) return r;
+    return nldsc::launch_band_f4_split(a, rs.tail_p, rest + rs.n_full, cp.n_rest - rs.n_full, e->gram.p, which, miss);
 }
 
 // An annotated run's request (nldsc_engine_run_annot): the caller's category-major arrays
@@ -1732,10 +1790,74 @@ int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, c
         HIPCHK(e->rep_items.ensure(slots));
     }
     if (L.shape.tail_p > 1) HIPCHK(e->gram.ensure((size_t)(L.n - L.shape.n_full) * L.shape.tail_p * 8192));
+    // add+dom column-pair rounds: the host waits for the two counts of the pair plan (as for the compacted count) and
+    // shapes the launches; with fewer pairs than the rounds need, the single-block plan runs as shaped above
+    nldsc::ColpairShape cp = {};
+    const int4 *cp_pairs = nullptr;
+    int4* cp_rest = nullptr;
+    const uint8_t* cp_miss = nullptr;
+    int n_cp_pairs = 0, n_cp_singles = 0;
+    // (routed runs: every kept pair holds an unrouted single block, so fewer of those than the rounds need pairs —
+    // missing-free data leaves none — settles it without the pair lists)
+    const int cp_round = e->colpair_round_items > 0 ? e->colpair_round_items : 4 * e->n_cu;
+    const bool cp_possible = !sc.use_t2 || (int64_t)L.n >= (int64_t)(e->colpair_round_items > 0 ? 1 : nldsc::COLPAIR_ROUND_MIN) * cp_round;
+    if (exact && sc.colpair && cp_possible) {
+        volatile int* tot = reinterpret_cast<volatile int*>(e->h_meta.p) + 8;
+        (void)spin_until_nonneg(tot);
+        (void)spin_until_nonneg(tot + 1);
+        HIPCHK(hipEventSynchronize(e->ev_route));
+        cp_pairs = e->items_p.p, cp_rest = e->items_s.p, n_cp_pairs = tot[0], n_cp_singles = tot[1];
+        if (sc.use_t2 && n_cp_pairs > 0) {
+            // routed: both lists compacted in order on the plan stream (idle by now; the super-item kernel runs
+            // meanwhile), so the rounds are sized by the pairs that keep a block; the main stream waits for the lists
+            hipStream_t ps = e->plan_stream;
+            const size_t cp_chunks = ((size_t)n_cp_pairs + 255) / 256, cs_chunks = ((size_t)n_cp_singles + 255) / 256;
+            HIPCHK(e->items_pu.ensure((size_t)n_items));
+            HIPCHK(e->items_su.ensure((size_t)n_items));
+            HIPCHK(e->compact_tmp2.ensure(cp_chunks + cs_chunks + 2));
+            int* tp = e->compact_tmp2.p;
+            int* ts = tp + cp_chunks + 1;
+            tot[2] = tot[3] = -1;
+            HIPCHK(nldsc::launch_compact_items(cp_pairs, n_cp_pairs, e->blk_miss.p, m.route_shift, s.nblk, tp,
+                                               tp + cp_chunks, e->items_pu.p, ps));
+            HIPCHK(nldsc::launch_compact_items(cp_rest, n_cp_singles, e->blk_miss.p, m.route_shift, s.nblk, ts,
+                                               ts + cs_chunks, e->items_su.p, ps));
+            HIPCHK(hipMemcpyAsync(e->h_meta.p + 10 * sizeof(int), tp + cp_chunks, sizeof(int), hipMemcpyDeviceToHost, ps));
+            HIPCHK(hipMemcpyAsync(e->h_meta.p + 11 * sizeof(int), ts + cs_chunks, sizeof(int), hipMemcpyDeviceToHost, ps));
+            HIPCHK(hipEventRecord(e->ev_route, ps));
+            (void)spin_until_nonneg(tot + 2);
+            (void)spin_until_nonneg(tot + 3);
+            HIPCHK(hipEventSynchronize(e->ev_route));
+            HIPCHK(hipStreamWaitEvent(st, e->ev_route, 0));
+            cp_pairs = e->items_pu.p, cp_rest = e->items_su.p, n_cp_pairs = tot[2], n_cp_singles = tot[3];
+            cp_miss = e->blk_miss.p;
+        }
+        cp = nldsc::shape_colpair(n_cp_pairs, n_cp_singles, s.n_it, e->n_cu, e->colpair_round_items, e->ksplit_ok,
+                                  s.replay && e->defer_rep, e->rep_gram_max_slots);
+    }
+    const bool colpair = cp.round_items > 0;
+    const int ksplit = colpair ? 1 : sc.ksplit;
+    if (colpair) {
+        const nldsc::SingleShape& rs = cp.rest;
+        e->last_ksplit = 1;
+        e->last_band_kernel = nldsc::band_kernel_code(false, e->t2_mode, s.path, 1, s.n_it, true);
+        e->last_round_items = 2 * cp.round_items;  // (in block pairs, the unit of band_items)
+        e->last_tail_ksplit = rs.tail_p;
+        if (rs.defer) {
+            const size_t slots = (size_t)cp.n_pair_full * 2 + (size_t)rs.n_full;
+            HIPCHK(e->rep_gram.ensure(std::max<size_t>(slots, 1) * 8192));
+            HIPCHK(e->rep_items.ensure(std::max<size_t>(slots, 1)));
+        }
+        if (rs.tail_p > 1) HIPCHK(e->gram.ensure((size_t)(cp.n_rest - rs.n_full) * rs.tail_p * 8192));
+        // the pairs past the last full round, as single blocks behind the leftover singles
+        HIPCHK(nldsc::launch_expand_pairs(cp_pairs + cp.n_pair_full, n_cp_pairs - cp.n_pair_full,
+                                          cp_rest + n_cp_singles, st));
+    }
     const auto t_wait1 = Clock::now();
     if (exact) {
         if (e->debug_timing) HIPCHK(hipEventRecord(e->ev_dbg[1], st));
-        if (run_single) HIPCHK(launch_single(e, a, s, m, sc.ksplit, L, 1));
+        if (colpair) HIPCHK(launch_colpair(e, a, cp, cp_pairs, cp_rest, cp_miss, 1));
+        else if (run_single) HIPCHK(launch_single(e, a, s, m, ksplit, L, 1));
         if (e->debug_timing) {
             HIPCHK(hipStreamSynchronize(st));
             float t_super = 0, t_gap = 0;
@@ -1748,7 +1870,8 @@ int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, c
     if (s.replay) {  // the KC launches, and the fp32 path, read the replayed tables
         HIPCHK(hipStreamWaitEvent(st, e->ev_replay, 0));
         if (exact && sc.use_t2) HIPCHK(launch_super(e, a, m, sc.n_items2, 2));
-        if (exact && run_single) HIPCHK(launch_single(e, a, s, m, sc.ksplit, L, 2));
+        if (exact && colpair) HIPCHK(launch_colpair(e, a, cp, cp_pairs, cp_rest, cp_miss, 2));
+        else if (exact && run_single) HIPCHK(launch_single(e, a, s, m, ksplit, L, 2));
     }
     if (n_items > 0 && !s.use_f4 && !s.use_i8) HIPCHK(nldsc::launch_band(a, 2, e->items.p, n_items));
     e->last_path = s.path;

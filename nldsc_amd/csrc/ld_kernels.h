@@ -109,6 +109,13 @@ hipError_t launch_plan(int n, int own_lo, int own_hi, const int* A, int* E, int*
                        hipStream_t st, bool pair = false, int4* small_items = nullptr);
 hipError_t launch_plan_emit(int n, const int2* rows, const int* meta, const int* offsets, int4* items, hipStream_t st,
                             bool pair = false);
+// The add+dom column-pair plan from the single-block plan's rows and meta (after launch_plan, pair false): the pairs
+// (I, J, 2) of each row's run in a tile and the odd runs' leftover singles (I, J, 1), each list in plan order
+// (capacities: the single-block item count); totals[0] = pairs, totals[1] = singles; counts_p / counts_s as `counts`.
+hipError_t launch_plan_split(int n, const int2* rows, const int* meta, int* counts_p, int* counts_s, int* totals,
+                             int4* pairs, int4* singles, hipStream_t st);
+// out[2 k], out[2 k + 1] = the single-block items of pairs[k] (n pairs)
+hipError_t launch_expand_pairs(const int4* pairs, int n, int4* out, hipStream_t st);
 // What every band launch of a run shares, filled once per run (ld_engine.cpp fill_band_args): the resident rows, the
 // per-SNP inputs, the pair epilogue's thresholds and accumulators, the replay and routing context, the stream.  The
 // launchers spread it over the kernels' flat __restrict__ parameter lists.
@@ -140,8 +147,9 @@ struct DeferredEpi { float* gram; int4* items; int* count; };
 // ones, so it is not part of the bundle.
 hipError_t launch_band(const BandArgs& a, int wps, const int4* items, int n_items);
 hipError_t launch_band_i8(const BandArgs& a, const int4* items, int n_items, int which);
-// exact path on fp4 MFMAs (N < 2^27), items (I, J0, 1, 0) (max_nc 1), or for additive-only unsegmented rows also
-// (I, J0, 2, 0) column-block pairs (max_nc 2; blk_miss then drops routed column blocks per block)
+// exact path on fp4 MFMAs (N < 2^27), items (I, J0, 1, 0) (max_nc 1), or for unsegmented rows also
+// (I, J0, 2, 0) column-block pairs (max_nc 2; blk_miss then drops routed column blocks per block): additive-only at two
+// waves per SIMD, add+dom at one (round_items then counts one-wave slots: 4 per CU)
 hipError_t launch_band_f4(const BandArgs& a, int max_nc, const int4* items, int n_items, int which,
                           const uint8_t* blk_miss, int round_items, const DeferredEpi* rep);
 // rep (unsegmented rows; or nullptr): the items holding a replayed rare variant run their K loops in the main launch and

@@ -1110,6 +1110,61 @@ __global__ void plan_emit_kernel(const int2* __restrict__ rows, int nblk, const 
     }
 }
 
+// ---- the add+dom column-pair plan (the one-wave 32 x 64 kernel, launch_band_f4 max_nc 2): the tiles and rows of the
+// single-block plan, each row's run in a tile split into its (I, J, 2) pairs and, for an odd run, the leftover single
+// (I, J, 1) — two lists, each in the single-block plan's order, so the pairs fill whole rounds of one-wave slots and the
+// singles go with the rest of the band to the two-wave kernel ----
+__global__ void plan_count_split_kernel(const int2* __restrict__ rows, int nblk, const int* __restrict__ meta,
+                                        int* __restrict__ counts_p, int* __restrict__ counts_s) {
+    const int n_t = (nblk + PLAN_R - 1) / PLAN_R, n_c = plan_n_c(meta);
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_t * n_c; k += gridDim.x * blockDim.x) {
+        const int T = k / n_c, c = k % n_c;
+        int cp = 0, cs = 0;
+        for (int I = T * PLAN_R; I < min(nblk, T * PLAN_R + PLAN_R); ++I) {
+            const int a = max(rows[I].x, c * PLAN_C), b = min(rows[I].y, c * PLAN_C + PLAN_C - 1);
+            if (a <= b) { cp += (b - a + 1) / 2; cs += (b - a + 1) & 1; }
+        }
+        counts_p[k] = cp;
+        counts_s[k] = cs;
+    }
+}
+
+// one workgroup: exclusive scans of both tile-count arrays in place; totals[0] = pairs, totals[1] = singles
+__global__ void __launch_bounds__(PLAN_WG) plan_scan_split_kernel(int* __restrict__ counts_p, int* __restrict__ counts_s,
+                                                                int nblk, const int* __restrict__ meta,
+                                                                int* __restrict__ totals) {
+    __shared__ int part[PLAN_WG];
+    const int n = (nblk + PLAN_R - 1) / PLAN_R * plan_n_c(meta);
+    const int tp = chunked_scan_excl<false>(counts_p, n, 0, part);  // (ends on a barrier: part is free again)
+    const int ts = chunked_scan_excl<false>(counts_s, n, 0, part);
+    if (threadIdx.x == 0) { totals[0] = tp; totals[1] = ts; }
+}
+
+__global__ void plan_emit_split_kernel(const int2* __restrict__ rows, int nblk, const int* __restrict__ meta,
+                                       const int* __restrict__ off_p, const int* __restrict__ off_s,
+                                       int4* __restrict__ pairs, int4* __restrict__ singles) {
+    const int n_t = (nblk + PLAN_R - 1) / PLAN_R, n_c = plan_n_c(meta);
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_t * n_c; k += gridDim.x * blockDim.x) {
+        const int T = k / n_c, c = k % n_c;
+        int op = off_p[k], os = off_s[k];
+        for (int I = T * PLAN_R; I < min(nblk, T * PLAN_R + PLAN_R); ++I) {
+            const int a = max(rows[I].x, c * PLAN_C), b = min(rows[I].y, c * PLAN_C + PLAN_C - 1);
+            int d = a;
+            for (; d < b; d += 2) pairs[op++] = make_int4(I, I + d, 2, 0);
+            if (d == b) singles[os++] = make_int4(I, I + d, 1, 0);
+        }
+    }
+}
+
+// the pairs past the last full round, back as the two single-block items each stands for
+__global__ void expand_pairs_kernel(const int4* __restrict__ pairs, int n, int4* __restrict__ out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int4 it = pairs[t];
+    out[2 * t] = make_int4(it.x, it.y, 1, 0);
+    out[2 * t + 1] = make_int4(it.x, it.y + 1, 1, 0);
+}
+
 // The whole schedule of a short slice in one workgroup (n <= PLAN_SMALL_N: a rank's shard of a chromosome): the right
 // pointers (plan_tile_max / tile_scan / right), the row ranges (plan_rows), the tile counts and their scan (plan_count /
 // plan_scan) and the items (plan_emit) — the same values, in one launch instead of seven on the critical path of a
@@ -2048,10 +2103,11 @@ __device__ __forceinline__ void band_f4_body(BandI8Lds& sh, const int4 it, const
     // chunks [t_lo, t_hi), t_lo and t_hi even (rows are padded to 64 bytes).  Two chunk buffers: P holds
     // even chunks, Q odd ones; each is reloaded right after its last word is decoded and read again two K
     // steps later, with no register copies of loads in flight (those would force vmcnt(0)).
-    // the strips' decode: with 64-bit shifts in the additive-only column-pair loop (decode_f4_64)
+    // the strips' decode: with 64-bit shifts in the additive-only column-pair loop (decode_f4_64); the add+dom
+    // column-pair loop (one wave per SIMD) measured faster on the 32-bit form (profiles/colpair_dom_loop_study.log)
     auto dec = [](auto WMc, uint32_t wa, uint32_t wb) __attribute__((always_inline)) {
         constexpr bool WM = decltype(WMc)::value;
-        if constexpr (NC == 2) return decode_f4_64<WM>(wa, wb);
+        if constexpr (NC == 2 && !DOM) return decode_f4_64<WM>(wa, wb);
         else return decode_f4<WM>(wa, wb);
     };
     auto kloop = [&](auto RMc, auto CMc, const int t_lo, const int t_hi) {
@@ -2211,9 +2267,10 @@ __device__ __forceinline__ bool routed_item(const uint8_t* blk_miss, int route_s
 }
 
 // One block pair per item.  WPS 2, except the segmented add+dom kernel (its int32 fold registers need 1).
-// NCX 2 (additive-only, unsegmented): items (I, J, 2) pair column blocks J and J + 1 in one wave (a 32 x 64 tile: the
+// NCX 2 (unsegmented): items (I, J, 2) pair column blocks J and J + 1 in one wave (a 32 x 64 tile: the
 // row strip decoded once for both), as the plan emits them with pairing; a column block the super-item routing sends
-// elsewhere (blk_miss) is dropped from its item here.
+// elsewhere (blk_miss) is dropped from its item here.  Add+dom pairs hold 16 accumulator tiles (256 AGPRs): WPS 1,
+// launched in rounds of one item per SIMD (launch_band_f4).
 template <bool DOM, int WPS, int SEG, bool KC, int NCX = 1>
 __global__ void __launch_bounds__(64, WPS) band_f4_kernel(const uint32_t* __restrict__ geno, int pitch_words, int n_it,
                                                         const SnpConst* __restrict__ cst, const int4* __restrict__ items,
@@ -2262,7 +2319,7 @@ __global__ void __launch_bounds__(64, WPS) band_f4_kernel(const uint32_t* __rest
     band_f4_body<DOM, NC_, DIAG_, SEG, KC>(sh, IT_, geno, pitch_words, n_it, cst, pos, Lw, Rw, sflags, n_snp, ld_wind, \
                                            n_org, rsq_thr, own_lo, own_hi, l2_acc, l2d_acc, ws_acc, tr)
     if constexpr (NCX == 2) {
-        static_assert(!DOM && SEG == 0, "column-block pairs: additive-only, unsegmented rows");
+        static_assert(SEG == 0 && (!DOM || WPS == 1), "column-block pairs: unsegmented rows; add+dom at 1 wave / SIMD");
         if (it.z == 2) {
             const int nblk = (n_snp + 31) >> 5;
             const bool r0 = blk_miss != nullptr && routed_item(blk_miss, route_shift, it.x, it.y, nblk);
@@ -3863,6 +3920,23 @@ hipError_t launch_plan_emit(int n, const int2* rows, const int* meta, const int*
     return hipGetLastError();
 }
 
+hipError_t launch_plan_split(int n, const int2* rows, const int* meta, int* counts_p, int* counts_s, int* totals,
+                             int4* pairs, int4* singles, hipStream_t st) {
+    const int nblk = (n + 31) / 32;
+    if (n <= 0) return hipMemsetAsync(totals, 0, 2 * sizeof(int), st);
+    hipLaunchKernelGGL(plan_count_split_kernel, dim3(256), dim3(256), 0, st, rows, nblk, meta, counts_p, counts_s);
+    hipLaunchKernelGGL(plan_scan_split_kernel, dim3(1), dim3(PLAN_WG), 0, st, counts_p, counts_s, nblk, meta, totals);
+    hipLaunchKernelGGL(plan_emit_split_kernel, dim3(256), dim3(256), 0, st, rows, nblk, meta, counts_p, counts_s, pairs,
+                       singles);
+    return hipGetLastError();
+}
+
+hipError_t launch_expand_pairs(const int4* pairs, int n, int4* out, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(expand_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pairs, n, out);
+    return hipGetLastError();
+}
+
 // A run's shared band arguments (BandArgs a) in the order the band kernels' flat parameter lists take them: the
 // resident rows, the per-SNP inputs, the pair epilogue's thresholds and accumulators.  Every band kernel is launched
 // with the XCD remap on (the 1 after A_EPI).
@@ -4101,8 +4175,8 @@ hipError_t launch_band_f4_deferred_epi(const BandArgs& a, int max_items, const D
 hipError_t launch_band_f4(const BandArgs& a, int max_nc, const int4* items, int n_items, int which,
                           const uint8_t* blk_miss, int round_items, const DeferredEpi* rep) {
     if (n_items <= 0) return hipSuccess;
-    // single block-pair items, or (additive-only, unsegmented rows) column-block pairs
-    if (max_nc != 1 && !(max_nc == 2 && !a.dom && a.n_it <= F4_SEG_CHUNKS)) return hipErrorInvalidValue;
+    // single block-pair items, or (unsegmented rows) column-block pairs: add+dom pairs at one wave per SIMD
+    if (max_nc != 1 && !(max_nc == 2 && a.n_it <= F4_SEG_CHUNKS)) return hipErrorInvalidValue;
     if (blk_miss != nullptr && a.n_it > F4_SEG_CHUNKS) return hipErrorInvalidValue;  // routing: unsegmented rows only
     const DeferredEpi none = {nullptr, nullptr, nullptr};
     const DeferredEpi& d = rep ? *rep : none;
@@ -4117,6 +4191,7 @@ hipError_t launch_band_f4(const BandArgs& a, int max_nc, const int4* items, int 
 #define NLDSC_BAND(DOM_, WPS_, SEG_, KC_) NLDSC_BAND_NC(DOM_, WPS_, SEG_, KC_, 1)
 #define NLDSC_PICK(KC_)                                                                                              \
     if (a.n_it > F4_SEG_CHUNKS) { if (a.dom) NLDSC_BAND(true, 1, F4_SEG_CHUNKS, KC_); else NLDSC_BAND(false, 2, F4_SEG_CHUNKS, KC_); } \
+    else if (a.dom && max_nc == 2) NLDSC_BAND_NC(true, 1, 0, KC_, 2);                                                \
     else if (a.dom) NLDSC_BAND(true, 2, 0, KC_);                                                                     \
     else if (max_nc == 2) NLDSC_BAND_NC(false, 2, 0, KC_, 2);                                                        \
     else NLDSC_BAND(false, 2, 0, KC_)

@@ -15,7 +15,7 @@ from . import _lib
 
 # nldsc_engine_band_kernel codes (include/nldsc_ld.h NLDSC_BAND_*)
 BAND_KERNELS = {0: "f32", 1: "i8", 2: "f4", 3: "f4_seg", 4: "f4_ksplit", 5: "f4_2x2", 6: "f4_routed",
-                7: "f4_quad"}
+                7: "f4_quad", 8: "f4_colpair"}
 
 
 def _torch_ready(*tensors):

@@ -3,6 +3,8 @@
 // output tile per wave on genotype-like planes (v = m + 2x, h, m; A1 allele frequency ~0.3, 1 % missing),
 // same FLOPs per iteration, operands held in registers (no memory traffic), 2 waves per SIMD.
 //   hipcc --offload-arch=gfx950 -O3 -o mfma_shape tools/study/mfma_shape.hip && ./mfma_shape [iters]
+//   ./mfma_shape <iters> 1: the band kernel's add+dom K loop, bare, on 32 x 32 tiles at 2 waves per SIMD against
+//   32 x 64 column-pair tiles at 1 wave per SIMD (kband below; profiles/colpair_dom_loop_study.log)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -208,8 +210,151 @@ __global__ void __launch_bounds__(64, 1) k64d(float* out, int iters) {
     out[blockIdx.x * 64 + lane] = acc;
 }
 
+// The band kernel's add+dom K loop as it is written there (two chunk buffers P / Q of 128 samples each, reloaded right
+// after their last word is decoded and fenced where they are written, two named fragment sets, VPM VALU slotted
+// after each MFMA), bare: no slot tables, no epilogue, every block holds missing calls.  NC 1 at 2 waves per SIMD is
+// the single-block loop (8 products per K step); NC 2 at 1 wave per SIMD is the 32 x 64 column-pair tile (16 products,
+// the row strip loaded and decoded once for both column blocks).  D64: the 64-bit-shift decode.  Each wave streams one
+// row strip and NC column strips out of NSTRIP strips of a C3 row block (2 466 chunks of 1 KiB), so a strip is read by
+// many waves of an XCD at about the same time and comes from L2, as in a round launch.
+constexpr int BAND_NSTRIP = 16, BAND_CHUNKS = 2466, BAND_STRIP_U4 = BAND_CHUNKS * 64;
+__device__ __forceinline__ Fr decf64(uint32_t wa, uint32_t wb) {
+    constexpr uint32_t M = 0x22222222u, K6 = 0x66666666u;
+    const uint64_t w = ((uint64_t)wb << 32) | wa;
+    uint64_t s1, s2, w2;
+    asm("v_lshlrev_b64 %0, 1, %1" : "=v"(s1) : "v"(w));
+    asm("v_lshrrev_b64 %0, 1, %1" : "=v"(s2) : "v"(w));
+    asm("v_lshrrev_b64 %0, 2, %1" : "=v"(w2) : "v"(w));
+    const uint32_t s1a = (uint32_t)s1, s1b = (uint32_t)(s1 >> 32), s2a = (uint32_t)s2, s2b = (uint32_t)(s2 >> 32);
+    const uint32_t w2a = (uint32_t)w2, w2b = (uint32_t)(w2 >> 32);
+    Fr f;
+    f.v = i32x4{(int)(s1a & K6), (int)(s2a & K6), (int)(s1b & K6), (int)(s2b & K6)};
+    f.h = i32x4{(int)(wa & M), (int)(w2a & M), (int)(wb & M), (int)(w2b & M)};
+    f.m = i32x4{(int)(s1a & ~wa & M), (int)(s2a & ~w2a & M), (int)(s1b & ~wb & M), (int)(s2b & ~w2b & M)};
+    return f;
+}
+template <int NC, int WPS, bool D64, int VPM>
+__global__ void __launch_bounds__(64, WPS) kband(float* out, const uint4* strips, int n_it) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int r = b % BAND_NSTRIP, c0 = (r + 1 + (b / BAND_NSTRIP) % (BAND_NSTRIP - 2)) % BAND_NSTRIP;
+    const uint4* rowp = strips + (size_t)r * BAND_STRIP_U4 + lane;
+    const uint4* colp[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        int s = (c0 + c) % BAND_NSTRIP;
+        if (c == 1 && s == r) s = (s + 1) % BAND_NSTRIP;
+        colp[c] = strips + (size_t)s * BAND_STRIP_U4 + lane;
+    }
+    f32x16 g[NC][8];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        for (int p = 0; p < 8; ++p) g[c][p] = f32x16{};
+    auto dec2 = [](uint32_t wa, uint32_t wb) __attribute__((always_inline)) { return D64 ? decf64(wa, wb) : decf(wa, wb); };
+    auto mfmas = [&](const Fr& a, const Fr (&bb)[NC]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            g[c][0] = m32(a.v, bb[c].v, g[c][0]); g[c][1] = m32(a.v, bb[c].m, g[c][1]);
+            g[c][2] = m32(a.v, bb[c].h, g[c][2]); g[c][3] = m32(a.m, bb[c].v, g[c][3]);
+            g[c][4] = m32(a.h, bb[c].v, g[c][4]); g[c][5] = m32(a.m, bb[c].m, g[c][5]);
+            g[c][6] = m32(a.m, bb[c].h, g[c][6]); g[c][7] = m32(a.h, bb[c].m, g[c][7]);
+        }
+#pragma unroll
+        for (int m = 0; m < 8 * NC; ++m) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
+        }
+    };
+    const int last = n_it - 1;
+    uint4 pr = rowp[0], qr = rowp[64], pc[NC], qc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { pc[c] = colp[c][0]; qc[c] = colp[c][64]; }
+    Fr a0 = dec2(pr.x, pr.y), a1, b0[NC], b1[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) b0[c] = dec2(pc[c].x, pc[c].y);
+    for (int t = 0; t < n_it; t += 2) {
+        a1 = dec2(pr.z, pr.w);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) b1[c] = dec2(pc[c].z, pc[c].w);
+        mfmas(a0, b0);
+        pr = rowp[64 * min(t + 2, last)];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) pc[c] = colp[c][64 * min(t + 2, last)];
+        __builtin_amdgcn_sched_barrier(0);
+        a0 = dec2(qr.x, qr.y);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) b0[c] = dec2(qc[c].x, qc[c].y);
+        mfmas(a1, b1);
+        a1 = dec2(qr.z, qr.w);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) b1[c] = dec2(qc[c].z, qc[c].w);
+        mfmas(a0, b0);
+        qr = rowp[64 * min(t + 3, last)];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) qc[c] = colp[c][64 * min(t + 3, last)];
+        __builtin_amdgcn_sched_barrier(0);
+        a0 = dec2(pr.x, pr.y);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) b0[c] = dec2(pc[c].x, pc[c].y);
+        mfmas(a1, b1);
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        for (int p = 0; p < 8; ++p)
+            for (int q = 0; q < 16; ++q) acc += g[c][p][q];
+    out[b * 64 + lane] = acc;
+}
+
+template <int NC, int WPS, bool D64, int VPM>
+static void run_band(const char* name, float* out, const uint4* strips, int grid, hipEvent_t e0, hipEvent_t e1, int rep) {
+    // the same products per launch for both tiles: grid x NC block pairs of one C3 row length
+    const double flop = (double)grid * NC * (BAND_CHUNKS * 2) * 8 * 2.0 * 32 * 32 * 64;
+    for (int w = 0; w < 8; ++w) {
+        if (w == 3) hipEventRecord(e0);
+        hipLaunchKernelGGL((kband<NC, WPS, D64, VPM>), dim3(grid), dim3(64), 0, 0, out, strips, BAND_CHUNKS);
+    }
+    hipEventRecord(e1);
+    hipEventSynchronize(e1);
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    ms /= 5;
+    printf("{\"loop\": \"%s\", \"decode\": \"%s\", \"valu_per_mfma_slot\": %d, \"rep\": %d, \"ms\": %.3f, "
+           "\"tflops\": %.1f}\n", name, D64 ? "64-bit shifts" : "32-bit", VPM, rep, ms, flop / (ms * 1e-3) / 1e12);
+    fflush(stdout);
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 2000;
+    if (argc > 2 && atoi(argv[2]) == 1) {  // the band K loop, 32 x 32 at 2 waves per SIMD against 32 x 64 at 1
+        const int grid = 256 * 8;
+        float* out;
+        uint4* strips;
+        const size_t n_u4 = (size_t)BAND_NSTRIP * BAND_STRIP_U4;
+        if (hipMalloc(&out, grid * 64 * sizeof(float)) != hipSuccess || hipMalloc(&strips, n_u4 * sizeof(uint4)) != hipSuccess)
+            return 2;
+        uint32_t* h = (uint32_t*)malloc(n_u4 * sizeof(uint4));
+        for (size_t k = 0; k < 4 * n_u4; ++k) {
+            uint32_t w = 0;
+            for (int j = 0; j < 16; ++j) {
+                uint32_t r = (uint32_t)((k * 16 + j) * 2654435761u) >> 22;
+                w |= (r < 10 ? 1u : r < 430 ? 2u : r < 520 ? 3u : 0u) << (2 * j);
+            }
+            h[k] = w;
+        }
+        hipMemcpy(strips, h, n_u4 * sizeof(uint4), hipMemcpyHostToDevice);
+        free(h);
+        hipEvent_t e0, e1;
+        hipEventCreate(&e0); hipEventCreate(&e1);
+        for (int rep = 0; rep < 3; ++rep) {
+            run_band<1, 2, false, 4>("32x32, 2 waves/SIMD", out, strips, grid, e0, e1, rep);
+            run_band<2, 1, true, 4>("32x64, 1 wave/SIMD", out, strips, grid / 2, e0, e1, rep);
+            run_band<2, 1, false, 4>("32x64, 1 wave/SIMD", out, strips, grid / 2, e0, e1, rep);
+            run_band<2, 1, true, 3>("32x64, 1 wave/SIMD", out, strips, grid / 2, e0, e1, rep);
+            run_band<2, 1, true, 5>("32x64, 1 wave/SIMD", out, strips, grid / 2, e0, e1, rep);
+            run_band<1, 2, true, 4>("32x32, 2 waves/SIMD", out, strips, grid, e0, e1, rep);
+        }
+        return hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess;
+    }
     const int grid = 256 * 8;  // 2 waves per SIMD on every CU
     float* out;
     hipMalloc(&out, grid * 64 * sizeof(float));
