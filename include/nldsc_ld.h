@@ -341,6 +341,12 @@ int nldsc_engine_band_tail_ksplit(const nldsc_engine* e);
                                    kernel; nldsc_engine_band_round_items then counts the block pairs of a pair
                                    round (two per pair item: 8 per CU), the unit of the work-item count */
 int nldsc_engine_band_kernel(const nldsc_engine* e);
+/* The column-pair rounds of the last run (NLDSC_BAND_F4_COLPAIR; all zero when no pair round ran): out[0] the pair
+ * items launched as pairs (whole rounds), out[1] the pairs the plan emitted (under super-item routing: those that keep
+ * a block after the compaction), out[2] the single-block items of the rest of the band (the odd runs' leftover singles
+ * and two for every pair past the last whole round; under routing before the kernel drops the routed ones of the
+ * latter).  Returns NLDSC_OK, or NLDSC_E_ARG for a NULL argument. */
+int nldsc_engine_band_pair_items(const nldsc_engine* e, int32_t out[3]);
 /* Where the last host-result run (nldsc_engine_run) wrote its owned slice: 1 straight into the caller's arrays (all
  * seven in nldsc_host_alloc buffers, zero copy), 0 through the engine's landing buffer and host copies, -1 no host
  * result written (device-table runs, empty owned ranges). */

@@ -37,6 +37,7 @@ EXPORTED = (
     "nldsc_engine_run_annot", "nldsc_ld_calculate_annot", "nldsc_annot_scale_exp", "nldsc_annot_plan_batches",
     "nldsc_engine_run_pairs", "nldsc_pairs_cell", "nldsc_pairs_window_blocks", "nldsc_pairs_split_ranges",
     "nldsc_engine_run_covar", "nldsc_ld_calculate_covar", "nldsc_engine_covar_projections",
+    "nldsc_engine_band_pair_items",
 )
 MAX_ANNOT = 1024  # NLDSC_MAX_ANNOT
 MAX_COVAR = 64  # NLDSC_MAX_COVAR
@@ -110,6 +111,8 @@ def lib(path: str | None = None) -> ctypes.CDLL:
             L.nldsc_engine_band_round_items.argtypes = [vp]
         if hasattr(L, "nldsc_engine_band_tail_ksplit"):
             L.nldsc_engine_band_tail_ksplit.argtypes = [vp]
+        if hasattr(L, "nldsc_engine_band_pair_items"):
+            L.nldsc_engine_band_pair_items.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
         if hasattr(L, "nldsc_engine_result_direct"):
             L.nldsc_engine_result_direct.argtypes = [vp]
         if hasattr(L, "nldsc_engine_run_device"):

@@ -347,6 +347,8 @@ struct nldsc_engine {
     size_t rep_gram_max_slots = (size_t)1 << 16;
     int last_ksplit = 1;
     int last_round_items = 0;
+    // nldsc_engine_band_pair_items: pair items launched as pairs, pairs the plan emitted, single-block items of the rest
+    int last_pair_items[3] = {0, 0, 0};
     int last_direct = -1;  // nldsc_engine_result_direct
     int last_tail_ksplit = 1;
     // fp4 band kernels on the GPU plan (option "t2"): 3 (default) missing-free 4 x 4 super-items in the quad
@@ -1019,6 +1021,7 @@ int run_nothing_owned(nldsc_engine* e, int M, int own, double* table_dev, int32_
     e->n_band_items = 0;
     e->last_ksplit = e->last_tail_ksplit = 1;
     e->last_round_items = 0;
+    e->last_pair_items[0] = e->last_pair_items[1] = e->last_pair_items[2] = 0;
     e->last_direct = -1;
     e->last_band_kernel = NLDSC_BAND_F4;
     if (table_dev) {
@@ -1568,6 +1571,7 @@ int enqueue_band_annot(nldsc_engine* e, const nldsc_ld_params* p, const RunShape
     e->n_band_items = n_items;
     e->last_ksplit = p_max;
     e->last_round_items = 0;
+    e->last_pair_items[0] = e->last_pair_items[1] = e->last_pair_items[2] = 0;
     e->last_tail_ksplit = 1;
     e->last_band_kernel = NLDSC_BAND_F4_KSPLIT;
     HIPCHK(e->gram.ensure(std::max<size_t>(units, 1) * 8192));
@@ -1610,6 +1614,7 @@ int enqueue_band_cov(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& 
     e->n_band_items = n_items;
     e->last_ksplit = p_max;
     e->last_round_items = 0;
+    e->last_pair_items[0] = e->last_pair_items[1] = e->last_pair_items[2] = 0;
     e->last_tail_ksplit = 1;
     e->last_band_kernel = NLDSC_BAND_F4_KSPLIT;
     HIPCHK(e->gram.ensure(std::max<size_t>(units, 1) * 8192));
@@ -1682,6 +1687,7 @@ int enqueue_band_pairs(nldsc_engine* e, const nldsc_ld_params* p, const RunShape
     e->n_band_items = n_items;
     e->last_ksplit = p_max;
     e->last_round_items = 0;
+    e->last_pair_items[0] = e->last_pair_items[1] = e->last_pair_items[2] = 0;
     e->last_tail_ksplit = 1;
     e->last_band_kernel = NLDSC_BAND_F4_KSPLIT;
     HIPCHK(e->gram.ensure(std::max<size_t>(units, 1) * 8192));
@@ -1783,6 +1789,7 @@ int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, c
     L.shape = nldsc::shape_single(L.n, s.n_it, e->n_cu, s.use_f4, sc.ksplit, e->band_rounds, m.nc2, e->ksplit_ok,
                                   s.replay && e->defer_rep, e->rep_gram_max_slots);
     e->last_round_items = L.shape.round_items;
+    e->last_pair_items[0] = e->last_pair_items[1] = e->last_pair_items[2] = 0;
     e->last_tail_ksplit = L.shape.tail_p;
     if (L.shape.defer && L.shape.n_full > 0) {
         const size_t slots = (size_t)L.shape.n_full * (m.nc2 ? 2 : 1);
@@ -1842,6 +1849,7 @@ int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, c
         e->last_ksplit = 1;
         e->last_band_kernel = nldsc::band_kernel_code(false, e->t2_mode, s.path, 1, s.n_it, true);
         e->last_round_items = 2 * cp.round_items;  // (in block pairs, the unit of band_items)
+        e->last_pair_items[0] = cp.n_pair_full, e->last_pair_items[1] = n_cp_pairs, e->last_pair_items[2] = cp.n_rest;
         e->last_tail_ksplit = rs.tail_p;
         if (rs.defer) {
             const size_t slots = (size_t)cp.n_pair_full * 2 + (size_t)rs.n_full;
@@ -2188,6 +2196,11 @@ int nldsc_engine_path(const nldsc_engine* e, int32_t* exact_i8, double* ops_alg_
 int nldsc_engine_ksplit(const nldsc_engine* e) { return e ? e->last_ksplit : NLDSC_E_ARG; }
 int nldsc_engine_band_round_items(const nldsc_engine* e) { return e ? e->last_round_items : NLDSC_E_ARG; }
 int nldsc_engine_band_tail_ksplit(const nldsc_engine* e) { return e ? e->last_tail_ksplit : NLDSC_E_ARG; }
+int nldsc_engine_band_pair_items(const nldsc_engine* e, int32_t out[3]) {
+    if (!e || !out) return NLDSC_E_ARG;
+    for (int k = 0; k < 3; ++k) out[k] = e->last_pair_items[k];
+    return NLDSC_OK;
+}
 int nldsc_engine_band_kernel(const nldsc_engine* e) { return e ? e->last_band_kernel : NLDSC_E_ARG; }
 
 int nldsc_engine_result_direct(const nldsc_engine* e) { return e ? e->last_direct : NLDSC_E_ARG; }

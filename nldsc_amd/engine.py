@@ -289,6 +289,10 @@ class Engine:
                                    if hasattr(self._L, "nldsc_engine_band_tail_ksplit") else 1),
                  result_direct=(self._L.nldsc_engine_result_direct(self._h)
                                 if hasattr(self._L, "nldsc_engine_result_direct") else -1))
+        cp = (ctypes.c_int32 * 3)()
+        if hasattr(L, "nldsc_engine_band_pair_items"):
+            L.nldsc_engine_band_pair_items(self._h, cp)
+        d.update(band_pair_items=cp[0], band_pairs=cp[1], band_pair_rest=cp[2])
         return d
 
 

@@ -33,6 +33,15 @@ def test_library_exports_every_declared_symbol():
     assert L.nldsc_version().decode() == "0.1.0"
 
 
+def test_band_pair_items_rejects_null_arguments():
+    """nldsc_engine_band_pair_items(e, out[3]): NLDSC_E_ARG for a NULL engine, the output untouched."""
+    from nldsc_amd import _lib
+    L = _lib.lib()
+    out = (ctypes.c_int32 * 3)(7, 8, 9)
+    assert L.nldsc_engine_band_pair_items(None, out) == _lib.E_ARG
+    assert list(out) == [7, 8, 9]
+
+
 def test_library_is_gfx950_code_object():
     from nldsc_amd import _lib
     data = open(_lib.LIB_PATH, "rb").read()

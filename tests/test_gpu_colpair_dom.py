@@ -10,7 +10,9 @@ the C oracle (default flags) or the fp64 truth (FLAG_EXACT_RARE) with the suite'
 Under super-item routing (missing-free blocks) both lists are compacted by the routing map and a pair may run with one
 block.  Production runs take pair rounds only on long rows (N >= 2^17) with at least two rounds of 4 pairs per CU; the option
 colpair_round_items sets the pairs per round for these shapes (N = 67: one chunk pair; N = 1 003), so the same
-kernels, plan split, expansion and launch shaping run on a few dozen items.  Which structures a case holds is
+kernels, plan split, expansion and launch shaping run on a few dozen items (the production gate itself, 1 024-chunk
+rows and saturated entries: test_gpu_colpair_long.py, test_gpu_saturation.py; production SNP counts:
+test_gpu_schedule_scale.py; the *_case builders here are theirs too).  Which structures a case holds is
 asserted from the host planner's paired plan (nldsc_plan_band, max_nc 2: the same runs of neighbouring column blocks,
 paired from each row's first needed block) and from what the engine reports (band kernel, block pairs per round)."""
 import numpy as np
@@ -142,12 +144,10 @@ def missing_in_blocks(N, M, blocks, seed):
     return g
 
 
-@pytest.mark.parametrize("N", [67, 1003])
-def test_row_and_column_missing_patterns(N):
-    """Blocks 0 and 5 of 8 hold missing calls and the window reaches three blocks ahead (two pair items per row): a
-    pair item's loop follows its row block and the union of its two column blocks, and all four (row, columns)
-    patterns occur — (0, 0)+(0, 1) and (4, 4)+(4, 5) with column blocks that differ in missingness.  Super-item
-    routing off (t2 0): the missing-free blocks would otherwise send the run to the super-item kernels."""
+def missing_patterns_case(N):
+    """Blocks 0 and 5 of 8 hold missing calls and the window reaches three blocks ahead (two pair items per row);
+    asserts that all four (row, columns) missingness patterns occur among the pair items.  Returns (rows, bed, M, run
+    arguments, pairs per round, options)."""
     from test_gpu_parity import missing_free_blocks
     M, wind, miss = 225, 0.9, {0, 5}
     rows, bed = pack(missing_in_blocks(N, M, sorted(miss), seed=N))
@@ -157,8 +157,17 @@ def test_row_and_column_missing_patterns(N):
     pats = {(int(I) in miss, int(J) in miss or int(J) + 1 in miss) for I, J, z, _ in items if z == 2}
     assert pats == {(False, False), (False, True), (True, False), (True, True)}, pats
     assert any(z == 2 and (int(J) in miss) != (int(J) + 1 in miss) for _, J, z, _ in items)
-    args = (wind, 0.0, 1e-5, 0.01, pos)
-    got, _ = ab(bed, M, N, args, flags=F4 | flag("FLAG_EXACT_RARE"), round_items=3, options={"t2": 0})
+    return rows, bed, M, (wind, 0.0, 1e-5, 0.01, pos), 3, {"t2": 0}
+
+
+@pytest.mark.parametrize("N", [67, 1003])
+def test_row_and_column_missing_patterns(N):
+    """Blocks 0 and 5 of 8 hold missing calls and the window reaches three blocks ahead (two pair items per row): a
+    pair item's loop follows its row block and the union of its two column blocks, and all four (row, columns)
+    patterns occur — (0, 0)+(0, 1) and (4, 4)+(4, 5) with column blocks that differ in missingness.  Super-item
+    routing off (t2 0): the missing-free blocks would otherwise send the run to the super-item kernels."""
+    rows, bed, M, args, round_items, options = missing_patterns_case(N)
+    got, _ = ab(bed, M, N, args, flags=F4 | flag("FLAG_EXACT_RARE"), round_items=round_items, options=options)
     if N == 1003:
         assert_ld_close(got, O.run_f64(rows, N, *args), tol=dict(l2=(1e-9, 1e-12), l2d=(1e-9, 1e-12),
                         residuals_std=(1e-12, 1e-10), maf=(0.0, 0.0)), label="colpair missing patterns")
@@ -174,16 +183,11 @@ def routed_map(M, miss, shift):
     return lambda I, J: free(int(I)) and free(int(J))
 
 
-@pytest.mark.parametrize("t2,shift", [(3, 2), (1, 1)], ids=["quad", "2x2"])
-def test_routing_drops_one_block_of_a_pair(t2, shift):
+def routing_case(N, t2, shift):
     """Mostly missing-free data under super-item routing: blocks 4-7 of 13 hold missing calls, every other block is
-    free.  The super-item kernel takes the missing-free super-items; of the pairs, those with both blocks routed
-    leave the compacted pair list, those with none run whole, and the pairs that straddle a super-column edge —
-    (1, 3)+(1, 4), (3, 3)+(3, 4): block 3 routed, block 4 not — lose exactly one block in the pair kernel (r0 / r1)
-    and run the single-block body on the other.  The last pairs' expanded single blocks go through the routing map
-    too.  Asserted from the paired plan and the blocks' missingness; bitwise option 0 (the routed single-block run)
-    with flop_issued equal, and held to the fp64 truth."""
-    N, M, wind, miss = 1003, 385, 0.9, {4, 5, 6, 7}
+    free; asserts from the paired plan and the blocks' missingness that pairs lose both, one and none of their blocks.
+    Returns (rows, bed, M, run arguments, pairs per round, options, the counts recorded)."""
+    M, wind, miss = 385, 0.9, {4, 5, 6, 7}
     rows, bed = pack(missing_in_blocks(N, M, sorted(miss), seed=11 + t2))
     pos = 0.01 * np.arange(M)
     routed = routed_map(M, miss, shift)
@@ -195,12 +199,25 @@ def test_routing_drops_one_block_of_a_pair(t2, shift):
     assert (1, 3) in pairs and routed(1, 3) and not routed(1, 4)
     round_items = 5
     assert kept >= round_items and kept % round_items, kept
-    args = (wind, 0.0, 1e-5, 0.01, pos)
-    got, t = ab(bed, M, N, args, flags=F4 | flag("FLAG_EXACT_RARE"), round_items=round_items,
-                options={"ksplit": 0, "t2": t2})
+    return (rows, bed, M, (wind, 0.0, 1e-5, 0.01, pos), round_items, {"ksplit": 0, "t2": t2},
+            dict(pairs=len(pairs), kept=kept, lose_one_block=one))
+
+
+@pytest.mark.parametrize("t2,shift", [(3, 2), (1, 1)], ids=["quad", "2x2"])
+def test_routing_drops_one_block_of_a_pair(t2, shift):
+    """Mostly missing-free data under super-item routing: blocks 4-7 of 13 hold missing calls, every other block is
+    free.  The super-item kernel takes the missing-free super-items; of the pairs, those with both blocks routed
+    leave the compacted pair list, those with none run whole, and the pairs that straddle a super-column edge —
+    (1, 3)+(1, 4), (3, 3)+(3, 4): block 3 routed, block 4 not — lose exactly one block in the pair kernel (r0 / r1)
+    and run the single-block body on the other.  The last pairs' expanded single blocks go through the routing map
+    too.  Asserted from the paired plan and the blocks' missingness; bitwise option 0 (the routed single-block run)
+    with flop_issued equal, and held to the fp64 truth."""
+    N = 1003
+    rows, bed, M, args, round_items, options, counts = routing_case(N, t2, shift)
+    got, t = ab(bed, M, N, args, flags=F4 | flag("FLAG_EXACT_RARE"), round_items=round_items, options=options)
     assert_ld_close(got, O.run_f64(rows, N, *args), tol=dict(l2=(1e-9, 1e-12), l2d=(1e-9, 1e-12),
                     residuals_std=(1e-12, 1e-10), maf=(0.0, 0.0)), label="colpair under routing")
-    record(f"colpair_dom_routed_t2_{t2}", dict(pairs=len(pairs), kept=kept, lose_one_block=one))
+    record(f"colpair_dom_routed_t2_{t2}", counts)
 
 
 def test_unfused_plan_chain():
@@ -212,13 +229,11 @@ def test_unfused_plan_chain():
        options={"plan_fused": 0})
 
 
-@pytest.mark.parametrize("defer", [1, 0], ids=["deferred", "kc_launch"])
-def test_one_replayed_block_in_a_pair(defer):
-    """One rare variant (8 hom-A2 and 60 het calls: replayed) in block 3 only: the pair (2, 2)+(2, 3) holds it in
-    one of its three blocks, so its clean block pair (2, 2) goes through the deferred (or KC) epilogue with it, where
-    option 0 runs (2, 2) in the main launch; (3, 3)+(3, 4) holds it in the row block."""
+def one_replayed_case(N):
+    """One rare variant (8 hom-A2 and 60 het calls: replayed) in block 3 only; asserts that the pair (2, 2)+(2, 3) is
+    planned.  Returns (bed, M, run arguments, pairs per round)."""
     from nldsc_amd import synth
-    N, M, wind = 1003, 225, 0.5
+    M, wind = 225, 0.5
     g = geno(N, M, seed=N + M, missing=0.01)
     rng = np.random.default_rng(21)
     pick = rng.choice(N, 68, replace=False)
@@ -228,8 +243,17 @@ def test_one_replayed_block_in_a_pair(defer):
     bed = synth.bed_bytes(rows)
     pos = 0.01 * np.arange(M)
     assert any(z == 2 and (int(I), int(J)) == (2, 2) for I, J, z, _ in paired_plan(pos, wind))
-    args = (wind, 1e-4, 1e-5, 0.01, pos)
-    got, _ = ab(bed, M, N, args, flags=F4, round_items=3, options={"defer_rep": defer})
+    return bed, M, (wind, 1e-4, 1e-5, 0.01, pos), 3
+
+
+@pytest.mark.parametrize("defer", [1, 0], ids=["deferred", "kc_launch"])
+def test_one_replayed_block_in_a_pair(defer):
+    """One rare variant (8 hom-A2 and 60 het calls: replayed) in block 3 only: the pair (2, 2)+(2, 3) holds it in
+    one of its three blocks, so its clean block pair (2, 2) goes through the deferred (or KC) epilogue with it, where
+    option 0 runs (2, 2) in the main launch; (3, 3)+(3, 4) holds it in the row block."""
+    N = 1003
+    bed, M, args, round_items = one_replayed_case(N)
+    got, _ = ab(bed, M, N, args, flags=F4, round_items=round_items, options={"defer_rep": defer})
     if defer:
         assert_ld_close(got, O.run_c(bed, M, N, *args), label="colpair, one replayed block vs oracle")
 

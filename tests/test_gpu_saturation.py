@@ -18,7 +18,9 @@ Two things differ from a literal reading of the kernel comments, both read from 
 128-sample chunks, is always even (rows are padded to 64 bytes), so N = 2^19 + 128 and 2^19 + 132 both run 4 098
 chunks: a final segment of 2 chunks, of which the second is all padding (N = 2^19 + 128) or holds 4 samples;
 (2) launches of one round of wave slots (option band_rounds) need 8 items per CU, far more than the 6 items of 70
-SNPs: test_round_launches_on_saturated_rows repeats the 70 rows to 2 048 SNPs for that path.
+SNPs: test_round_launches_on_saturated_rows repeats the 70 rows to 2 048 SNPs for that path (its truth by multiplicity,
+multiplicity_truth, is test_gpu_colpair_long.py's too).  The add+dom column-pair tile (16 accumulator tiles, one wave
+per SIMD) takes the same 70 rows through the round option colpair_round_items: PATHS colpair*.
 
 Out of scope: N near 2^27, the int32 limit of an entry (16 N < 2^31) — a data set there is gigabytes and its truth
 takes minutes.
@@ -237,6 +239,61 @@ def bitwise(got, ref, label):
         np.testing.assert_array_equal(got[k], ref[k], err_msg=f"{label} {k}")
 
 
+def exact_pairs(rows, N):
+    """(pairs, own) of a few distinct rows: O.pair_r2_f64 of every row against all others (one window), and of every
+    row beside a copy of itself — a copy of row j has r = 1 and the dominance pair r2d(j, j)."""
+    M = len(rows)
+    pairs = O.pair_r2_f64(rows, N, LD_WIND, 0.0, STD_THR, np.arange(M) * 0.01, np.arange(M))
+    # (rows beside their copies, every other SNP out of the window)
+    own = O.pair_r2_f64(np.repeat(rows, 2, axis=0), N, LD_WIND, 0.0, STD_THR,
+                        np.repeat(np.arange(M) * 10.0, 2), 2 * np.arange(M))
+    return pairs, own
+
+
+def exact_r2d(pairs_own):
+    """Every exact dominance r2adj that enters a score of the repeated rows."""
+    pairs, own = pairs_own
+    return np.concatenate([p[3] for p in pairs] + [p[3] for p in own])
+
+
+def multiplicity_truth(pairs_own, reps, rsq, per_snp):
+    """The truth of `reps` SNPs that repeat M distinct rows in turn (SNP j holds row j % M), all in one window, from
+    the rows' exact pairs: SNP j's neighbours are mult[k] copies of every other row and mult[j] - 1 of its own.
+    per_snp: the M rows' own truth (maf, residuals_std; the arrays' dtypes)."""
+    pairs, own = pairs_own
+    M = len(pairs)
+    mult = np.bincount(np.arange(reps) % M, minlength=M)
+    exp = {k: np.empty(reps, v.dtype) for k, v in per_snp.items()}
+    for j in range(M):
+        ks, r2a, kds, r2d = pairs[j]
+        assert len(ks) == M - 1 and len(kds) == M - 1
+        ks2, r2a2, kds2, r2d2 = own[j]
+        assert list(ks2) == [2 * j + 1] and list(kds2) == [2 * j + 1]
+        a_self, d_self = r2a2[0], r2d2[0]
+        sel = np.arange(j, reps, M)
+        exp["l2"][sel] = 1.0 + (mult[ks] * r2a).sum() + (mult[j] - 1) * a_self
+        exp["l2d"][sel] = (mult[kds] * r2d).sum() + (mult[j] - 1) * d_self
+        exp["l2d_wse"][sel] = (mult[kds] * (r2d > rsq)).sum() + (mult[j] - 1) * (d_self > rsq)
+        assert abs(d_self - rsq) > 1e-6
+        for k in ("maf", "residuals_std"):
+            exp[k][sel] = per_snp[k][j]
+    exp["l2_ws"][:] = exp["l2d_ws"][:] = reps - 1
+    return exp
+
+
+def check_multiplicity(got, exp, label):
+    """The exact-path bar per SNP: L2 / L2D within 1e-9 + 1e-12 |x|, MAF and the counts equal, residual std at rtol
+    1e-12."""
+    for k in ("l2", "l2d"):
+        err = np.abs(got[k] - exp[k])
+        lim = 1e-9 + 1e-12 * np.abs(exp[k])
+        print(f"{label} {k}: worst |d| {err.max():.3g}, {(err / lim).max():.3g} x the bound")
+        assert (err <= lim).all(), k
+    for k in ("maf", "l2_ws", "l2d_ws", "l2d_wse"):
+        np.testing.assert_array_equal(got[k], exp[k], err_msg=k)
+    np.testing.assert_allclose(got["residuals_std"], exp["residuals_std"], rtol=1e-12, atol=0.0)
+
+
 _runs: dict = {}
 
 
@@ -259,6 +316,11 @@ def run(case, flags, opts=None, want_kernel=None):
 
 SINGLE = {"ksplit": 0, "t2": 0, "f4_nc2": 0}  # one launch of single-block items: the kernel the others are held to
 
+def pair_lists(t):
+    """(pair items launched as pairs, pairs the plan emitted, single-block items of the rest) of a run's timings."""
+    return t["band_pair_items"], t["band_pairs"], t["band_pair_rest"]
+
+
 # the unsegmented paths at N = 2^19: (case, additive-only, options, band kernel, timings that must hold)
 PATHS = {
     "ksplit": ("n2p19", False, {"t2": 0}, "f4_ksplit", lambda t: t["ksplit"] > 1),
@@ -272,6 +334,18 @@ PATHS = {
     "t2_2x2": ("n2p19_free", False, {"ksplit": 0, "t2": 2}, "f4_2x2", lambda t: True),
     "t2_quad": ("n2p19_free", False, {"ksplit": 0, "t2": 3}, "f4_quad", lambda t: True),
     "t2_quad_additive": ("n2p19_free", True, {"ksplit": 0, "t2": 3}, "f4_quad", lambda t: True),
+    # add+dom column-pair rounds (the one-wave 32 x 64 tile, 16 accumulator tiles, 4 096 chunks): the 3 blocks' 6 block
+    # pairs are the pair items (0, 0)+(0, 1) and (1, 1)+(1, 2) — both diagonal, the second with the 6-SNP last block —
+    # and the leftover singles (0, 2) and (2, 2); in one round of 2 pairs and in two of 1
+    "colpair": ("n2p19", False, {"t2": 0, "colpair_round_items": 2}, "f4_colpair",
+                lambda t: t["band_round_items"] == 4 and pair_lists(t) == (2, 2, 2) and t["ksplit"] == 1),
+    "colpair_one_per_round": ("n2p19", False, {"t2": 0, "colpair_round_items": 1}, "f4_colpair",
+                              lambda t: t["band_round_items"] == 2 and pair_lists(t) == (2, 2, 2) and t["ksplit"] == 1),
+    "colpair_missing_free": ("n2p19_free", False, {"t2": 0, "colpair_round_items": 2}, "f4_colpair",
+                             lambda t: t["band_round_items"] == 4 and pair_lists(t) == (2, 2, 2)),
+    # every block routed to the quad kernel: no pair keeps a block, and the run reports the quad kernel
+    "colpair_routed": ("n2p19_free", False, {"ksplit": 0, "t2": 3, "colpair_round_items": 2}, "f4_quad",
+                       lambda t: t["band_round_items"] == 0 and pair_lists(t) == (0, 0, 0)),
     "defaults": ("n2p19", False, {}, None, lambda t: True),
     "defaults_missing_free": ("n2p19_free", False, {}, None, lambda t: True),
 }
@@ -366,34 +440,6 @@ class TestGpu:
                 assert (t["band_round_items"] > 0) == bool(rounds) and t["band_items"] == 2080, t
                 assert t["band_kernel"] == "f4" and t["ksplit"] == 1, t
         bitwise(out[1], out[0], "round launches")
-        # the exact pairs of the 70 rows; a copy of row j itself has r = 1 and its dominance pair r2d(j, j)
-        pairs = O.pair_r2_f64(rows, N, LD_WIND, 0.0, STD_THR, np.arange(M) * 0.01, np.arange(M))
-        # (rows beside their copies, every other SNP out of the window)
-        own = O.pair_r2_f64(np.repeat(rows, 2, axis=0), N, LD_WIND, 0.0, STD_THR,
-                            np.repeat(np.arange(M) * 10.0, 2), 2 * np.arange(M))
-        mult = np.bincount(np.arange(reps) % M, minlength=M)
-        exp = {k: np.empty(reps, v.dtype) for k, v in truth(case).items()}
-        for j in range(M):
-            ks, r2a, kds, r2d = pairs[j]
-            assert len(ks) == M - 1 and len(kds) == M - 1
-            ks2, r2a2, kds2, r2d2 = own[j]
-            assert list(ks2) == [2 * j + 1] and list(kds2) == [2 * j + 1]
-            a_self, d_self = r2a2[0], r2d2[0]
-            sel = np.arange(j, reps, M)
-            exp["l2"][sel] = 1.0 + (mult[ks] * r2a).sum() + (mult[j] - 1) * a_self
-            exp["l2d"][sel] = (mult[kds] * r2d).sum() + (mult[j] - 1) * d_self
-            exp["l2d_wse"][sel] = (mult[kds] * (r2d > rsq)).sum() + (mult[j] - 1) * (d_self > rsq)
-            assert abs(d_self - rsq) > 1e-6
-            for k in ("maf", "residuals_std"):
-                exp[k][sel] = truth(case)[k][j]
-        exp["l2_ws"][:] = exp["l2d_ws"][:] = reps - 1
+        exp = multiplicity_truth(exact_pairs(rows, N), reps, rsq, truth(case))
         # the same exact-path bar per SNP, over 2 047 neighbours here
-        got = out[1]
-        for k in ("l2", "l2d"):
-            err = np.abs(got[k] - exp[k])
-            lim = 1e-9 + 1e-12 * np.abs(exp[k])
-            print(f"round launches {k}: worst |d| {err.max():.3g}, {(err / lim).max():.3g} x the bound")
-            assert (err <= lim).all(), k
-        for k in ("maf", "l2_ws", "l2d_ws", "l2d_wse"):
-            np.testing.assert_array_equal(got[k], exp[k], err_msg=k)
-        np.testing.assert_allclose(got["residuals_std"], exp["residuals_std"], rtol=1e-12, atol=0.0)
+        check_multiplicity(out[1], exp, "round launches")

@@ -15,8 +15,14 @@ quadratic test_plan.gpu_schedule_restated is its reference at small n).
 The tests without the gpu mark check the helpers and that every geometry really reaches the sizes it is here for, from
 the restatement alone.
 
-Out of scope: K-split, round launches and segmented rows (long rows: test_gpu_parity.py, test_gpu_saturation.py),
-unsorted or negative positions (the host plan), split-halo runs.
+The add+dom column-pair plan (plan_*_split, expand_pairs_kernel, the second compaction of its two lists under routing,
+launch_colpair) runs on the same geometries through the engine option colpair_round_items at the production round of
+4 pairs per CU: on these short rows the option stands in for the row-length gate only (test_gpu_colpair_long.py runs
+the gate itself), the rounds, the list sizes and the launches are production's.  The lists' sizes as the engine
+reports them (nldsc_engine_band_pair_items) are held to the restatement (split_totals, split_kept).
+
+Out of scope: K-split, round launches of the single-block kernel and segmented rows (long rows: test_gpu_parity.py,
+test_gpu_saturation.py), unsorted or negative positions (the host plan), split-halo runs.
 """
 import functools
 import os
@@ -109,6 +115,59 @@ def _ceil(a, b):
     return -(-a // b)
 
 
+def _split_pieces(d0, d1):
+    """Per 16-offset tile column c: (a, b, run) of every row's piece [a, b] of its offsets [d0, d1] (run 0: none)."""
+    top = int(np.where(d0 <= d1, d1 + 1, 0).max(initial=0))
+    for c in range(_ceil(top, 16)):
+        a, b = np.maximum(d0, 16 * c), np.minimum(d1, 16 * c + 15)
+        yield a, b, np.where(a <= b, b - a + 1, 0)
+
+
+def split_totals(d0, d1):
+    """(pairs, singles, odd pieces per row) of the add+dom split plan on these row ranges."""
+    pairs, singles, odd = 0, 0, np.zeros(len(d0), np.int64)
+    for _, _, run in _split_pieces(d0, d1):
+        pairs += int((run // 2).sum())
+        singles += int((run & 1).sum())
+        odd += run & 1
+    return pairs, singles, odd
+
+
+def blocks_with_missing(rows, n_org):
+    """bool per 32-SNP block: it holds a missing call among the slots the reference reads (the engine's blk_miss;
+    test_gpu_parity.missing_free_blocks counts the others)."""
+    rows = np.asarray(rows, np.uint8)
+    M, nb = rows.shape
+    miss = np.stack([((rows >> (2 * k)) & 3) == 1 for k in range(4)], axis=-1)
+    r = n_org % 4
+    keep = [k >= 4 - r for k in range(4)] if r else [True] * 4
+    row_miss = miss[:, :nb - 1, :].any(axis=(1, 2)) | miss[:, nb - 1, keep].any(axis=1)
+    pad = np.zeros(_ceil(M, 32) * 32, bool)
+    pad[:M] = row_miss
+    return pad.reshape(-1, 32).any(axis=1)
+
+
+def split_kept(s, blk_miss, shift=2):
+    """(pairs, singles) the routing compaction keeps of the split plan's lists (ld_kernels.hip keep_item): block pair
+    (I, J) is routed to the super-item kernel when the 2^shift (clamped) blocks of its super-row and of its
+    super-column are all missing-free; a pair stays while one of its two block pairs is unrouted, a single while its
+    own is."""
+    nblk, F = s["nblk"], 1 << shift
+    g = np.arange(_ceil(nblk, F))
+    free = ~np.stack([blk_miss[np.minimum(F * g + k, nblk - 1)] for k in range(F)]).any(axis=0)
+    I = np.arange(nblk)
+
+    def routed(J):
+        return free[I >> shift] & free[np.clip(J, 0, nblk - 1) >> shift]
+    pairs = singles = 0
+    for a, b, run in _split_pieces(s["d0"], s["d1"]):
+        for k in range(8):
+            d = a + 2 * k
+            pairs += int(((d + 1 <= b) & (run > 0) & ~(routed(I + d) & routed(I + d + 1))).sum())
+        singles += int((((run & 1) == 1) & ~routed(I + b)).sum())
+    return pairs, singles
+
+
 def schedule_restated(pos, w, own=None):
     """The GPU schedule (ld_kernels.hip plan_edges / plan_right / plan_rows and the kernels counting on their rows)
     restated on whole arrays: edges A, E, right pointers R, per row block the useful offsets [d0, d1] (d0 > d1: none),
@@ -136,6 +195,9 @@ def schedule_restated(pos, w, own=None):
         a, b = np.maximum(d0, 16 * c), np.minimum(d1, 16 * c + 15)
         pair += int(np.where(a <= b, (b - a + 2) // 2, 0).sum())
     s["pair_items"] = pair
+    # add+dom (plan_count_split / plan_emit_split): each row's run in a tile column split into floor(run / 2) pairs
+    # (I, J, 2) and, for an odd run, one single; odd_pieces: per row, its pieces of odd length
+    s["split_pairs"], s["split_singles"], s["odd_pieces"] = split_totals(d0, d1)
     for shift, key, tr, tc in ((1, "t2", 16, 16), (2, "quad", 4, 8)):  # plan_rows2 and its count kernels
         F = 1 << shift
         nblk2 = _ceil(nblk, F)
@@ -393,6 +455,34 @@ def test_restatement_equals_quadratic_restatement(seed):
             items = _emit_loops(s["d0"], s["d1"], s["nblk"], pair)
             assert covered(items) == pairs and len(set(items)) == len(items)
             assert len(items) == (s["pair_items"] if pair else s["items"])
+        # the add+dom split plan, block pair by block pair: a row's needed offsets of one tile column, in order, are
+        # taken two at a time; the pairs and the singles together cover every block pair once
+        n_pair = n_single = 0
+        odd = np.zeros(s["nblk"], np.int64)
+        split = []
+        for I in range(s["nblk"]):
+            for c in range(_ceil(s["nblk"], 16) + 1):
+                piece = [J - I for (i, J) in sorted(pairs) if i == I and (J - I) // 16 == c]
+                for k in range(0, len(piece) - 1, 2):
+                    assert piece[k + 1] == piece[k] + 1
+                    split.append((I, I + piece[k], 2, 0))
+                if len(piece) % 2:
+                    split.append((I, I + piece[-1], 1, 0))
+                n_pair, n_single, odd[I] = n_pair + len(piece) // 2, n_single + len(piece) % 2, odd[I] + len(piece) % 2
+        assert covered(split) == pairs and sum(z for _, _, z, _ in split) == len(pairs)
+        assert (s["split_pairs"], s["split_singles"]) == (n_pair, n_single)
+        np.testing.assert_array_equal(s["odd_pieces"], odd)
+        assert s["split_pairs"] == s["items"] - s["pair_items"]
+        assert s["split_singles"] == 2 * s["pair_items"] - s["items"]
+        # ... and what the routing compaction keeps of both lists, for missing calls in a third of the blocks
+        blk_miss = rng.random(s["nblk"]) < 1.0 / 3.0
+        for shift in (1, 2):
+            def routed(I, J):
+                F = 1 << shift
+                return not any(blk_miss[min(F * (b // F) + k, s["nblk"] - 1)] for b in (I, J) for k in range(F))
+            kept_p = sum(not (routed(I, J) and routed(I, J + 1)) for I, J, z, _ in split if z == 2)
+            kept_s = sum(not routed(I, J) for I, J, z, _ in split if z == 1)
+            assert split_kept(s, blk_miss, shift) == (kept_p, kept_s)
         for shift, key in ((1, "t2"), (2, "quad")):
             F, cnt = 1 << shift, 0
             for I2 in range(_ceil(s["nblk"], F)):
@@ -440,6 +530,35 @@ def test_geometries_reach_the_scans_they_are_here_for(name):
         gap = np.diff(g["pos"])
         assert np.median(gap[gap > 0]) * 100 < np.quantile(gap, 0.99) and (gap > g["w"]).sum() >= 4
     assert s["items"] / 2 <= s["pair_items"] < s["items"]
+    # the add+dom split plan (test_add_dom_column_pair_rounds and the cases after it), at the MI355X's 256 CUs: at
+    # least two rounds of 4 pairs per CU, and a last partial round whose pairs expand_pairs_kernel turns back into
+    # single-block items
+    rnd = 4 * 256
+    assert s["split_pairs"] == s["items"] - s["pair_items"] and s["split_singles"] == 2 * s["pair_items"] - s["items"]
+    assert s["split_pairs"] >= 2 * rnd and s["split_singles"] > 0
+    if name == "fused_full":
+        # every block pair of 1 024 blocks: sum floor(n / 2) = 2^18 pairs, exactly 256 rounds — the edge without a
+        # partial round (nothing to expand); chain_first, one block more, has the same band with one
+        assert s["split_pairs"] == 256 * rnd
+    else:
+        assert s["split_pairs"] % rnd != 0
+    if name in ("wide_100k", "fused_full"):
+        assert s["split_pairs"] > 65536  # (launch_compact_items over more than 256 chunks of pairs under routing)
+    if name == "wide_100k":
+        assert _ceil(int((s["d1"] + 1).max()), 16) > 1  # more than one tile column
+    # a whole run's rows start at offset 0, so every tile-column edge falls on an even offset and only a row's last
+    # piece can be odd; an owned range's left halo rows start at J0 - I > 0: there a run is cut into two odd pieces,
+    # two singles, where pairing from the row's first block (the host planner's) leaves none
+    assert s["odd_pieces"].max() == 1
+    if name in OWNED:
+        so = restated(name, own_ranges(M)[0])
+        two = (so["odd_pieces"] == 2) & ((so["d1"] - so["d0"] + 1) % 2 == 0)
+        assert two.any() and so["split_pairs"] >= 2 * rnd and so["split_pairs"] % rnd != 0
+        assert so["split_singles"] > int(((so["d1"] - so["d0"] + 1)[so["d0"] <= so["d1"]] % 2).sum())
+    if name == "narrow_65k":
+        assert s["items"] <= 1 << 16  # the deferred-epilogue slots hold a default-flags run's block pairs
+    if name == "wide_100k":
+        assert s["items"] > 1 << 16   # ... and here they do not: the KC launch after the replay
     _, _, host = _lib.plan_band(g["pos"], np.ones(M, np.uint8), g["w"], max_nc=1)
     assert len(host) <= s["items"]
     n_fail = {}
@@ -448,6 +567,15 @@ def test_geometries_reach_the_scans_they_are_here_for(name):
         n_fail[missing] = int((~d.passed).sum())
         assert n_fail[missing] >= 0.03 * M and (d.wsd < d.wsa).any()
         assert {"rate": d.free == 0, "none": d.free == nblk, "mixed4": 0 < d.free < nblk}[missing]
+        bm = blocks_with_missing(d.rows, N_ORG)
+        assert len(bm) == nblk and int((~bm).sum()) == d.free
+        kept = split_kept(s, bm)
+        if missing == "rate":
+            assert kept == (s["split_pairs"], s["split_singles"])
+        if missing == "none":
+            assert kept == (0, 0)
+        if missing == "mixed4":  # routed runs still fill pair rounds, and not in whole rounds
+            assert rnd <= kept[0] < s["split_pairs"] and kept[0] % rnd != 0 and 0 < kept[1] <= s["split_singles"]
 
 
 def test_target_truth_guards_its_threshold():
@@ -465,9 +593,10 @@ def test_target_truth_guards_its_threshold():
 # GPU runs
 # ---------------------------------------------------------------------------------------------------------------
 
-def gpu_run(d, options, want, *, mode="f4", dom=True, own=None):
+def gpu_run(d, options, want, *, mode="f4", dom=True, own=None, round_items=0):
     """One run on a fresh engine with these options; the kernel it took is the one the data and options dictate
-    (`want`: the super-item kernels only with routing candidates, test_gpu_parity's missing_free_blocks rule)."""
+    (`want`: the super-item kernels only with routing candidates, test_gpu_parity's missing_free_blocks rule), in
+    launches of `round_items` block pairs (0: one launch)."""
     from nldsc_amd.engine import Engine
     rsq, _ = d.truth()
     flags = MODES[mode] | _lib_flag("FLAG_EXACT_RARE") | (0 if dom else _lib_flag("FLAG_ADDITIVE_ONLY"))
@@ -476,7 +605,7 @@ def gpu_run(d, options, want, *, mode="f4", dom=True, own=None):
         got = e.run(d.w, MAF, STD_THR, rsq, d.pos, flags=flags, own=own)
         t = e.timings()
     assert t["band_kernel"] == want, (d.name, d.missing, options, t["band_kernel"], want, d.free)
-    assert t["ksplit"] == 1 and t["band_round_items"] == 0
+    assert t["ksplit"] == 1 and t["band_round_items"] == round_items, (t["ksplit"], t["band_round_items"], round_items)
     check_run(d, got, own=own, dom=dom, label=f"{d.name} {d.missing} {options} {mode} own {own}")
     return got, t
 
@@ -605,3 +734,104 @@ def test_owned_ranges(data, name, k, missing):
     host, th = gpu_run(d, {"gpu_plan": 0}, "f4", own=own)
     assert 0 < th["band_items"] <= s["items"]
     same_gram(owned(got, own), owned(host, own), f"{name} {missing} own {own} vs host plan")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the add+dom column-pair plan (plan_*_split, expand_pairs_kernel, the second compaction under routing,
+# launch_colpair) in rounds of the production size, 4 pairs per CU
+# ---------------------------------------------------------------------------------------------------------------
+
+def cu_count():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def expected_pair_rounds(d, s, rnd):
+    """(band kernel, band_round_items, (pairs launched, pairs emitted, single-block items of the rest)) of an add+dom
+    run of data set d on the restated schedule s with rounds of rnd pairs.  The rule: the split plan's pairs — under
+    super-item routing (missing-free blocks: d.free > 0) those the compaction keeps, split_kept — run in pair rounds
+    when they fill one round (the round option's minimum) and the band holds two rounds of block pairs; whole rounds
+    only, every pair past them back as two single-block items behind the (kept) leftover singles.  Otherwise no pair
+    item runs and the run reports the kernel it took before."""
+    plain = "f4" if d.free == 0 else "f4_quad"
+    pairs, singles = (s["split_pairs"], s["split_singles"]) if d.free == 0 else \
+        split_kept(s, blocks_with_missing(d.rows, N_ORG))
+    if pairs < rnd or s["items"] < 2 * rnd:
+        return plain, 0, (0, 0, 0)
+    return "f4_colpair", 2 * rnd, (pairs // rnd * rnd, pairs, singles + 2 * (pairs % rnd))
+
+
+def pair_rounds_ab(d, s, options, *, own=None):
+    """The add+dom run in pair rounds of 4 per CU against the same run with f4_nc2_dom 0: the kernel, the round and
+    the three list sizes the restatement gives, everything check_run checks on both, bitwise equal arrays, equal
+    flop_issued and band_items."""
+    rnd = 4 * cu_count()
+    want, round_items, lists = expected_pair_rounds(d, s, rnd)
+    opts = dict(options, colpair_round_items=rnd)
+    a, ta = gpu_run(d, dict(opts, f4_nc2_dom=1), want, own=own, round_items=round_items)
+    b, tb = gpu_run(d, dict(opts, f4_nc2_dom=0), "f4" if d.free == 0 else "f4_quad", own=own)
+    got = (ta["band_pair_items"], ta["band_pairs"], ta["band_pair_rest"])
+    assert got == lists, (d.name, d.missing, options, own, got, lists)
+    assert (tb["band_pair_items"], tb["band_pairs"], tb["band_pair_rest"]) == (0, 0, 0), tb
+    assert ta["band_items"] == tb["band_items"] == s["items"], (ta["band_items"], tb["band_items"], s["items"])
+    assert ta["flop_issued"] == tb["flop_issued"] > 0, (ta["flop_issued"], tb["flop_issued"])
+    bitwise(a, b, f"{d.name} {d.missing} {options} own {own}: f4_nc2_dom 1 vs 0")
+    return want, lists
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fused", [1, 0], ids=["default_plan", "chain"])
+@pytest.mark.parametrize("missing", ["rate", "mixed4"])
+@pytest.mark.parametrize("name", sorted(GEOMS))
+def test_add_dom_column_pair_rounds(data, name, missing, fused):
+    """Add+dom in pair rounds of the production size at production SNP counts: the split plan over many tile columns
+    and multi-chunk scans of both count arrays (behind the fused plan up to 32 768 SNPs, behind the chain with
+    plan_fused 0), the last pairs through expand_pairs_kernel, and with missing-free groups of blocks ("mixed4") the
+    second compaction of both lists beside the quad kernel."""
+    d, s = data(name, missing), restated(name)
+    want, lists = pair_rounds_ab(d, s, {} if fused else {"plan_fused": 0})
+    if cu_count() == 256:  # (test_geometries_reach_the_scans_they_are_here_for asserts these sizes for 256 CUs)
+        assert want == "f4_colpair" and lists[0] >= 1024, (want, lists)
+        assert (lists[1] % 1024 == 0) == ((name, missing) == ("fused_full", "rate")), lists
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", range(3))
+@pytest.mark.parametrize("name", OWNED)
+def test_add_dom_column_pair_rounds_on_owned_ranges(data, name, k):
+    """Owned ranges: the left halo's rows start at offset J0 - I > 0, so their runs are cut at tile-column edges into
+    pieces the host planner's pairing does not have (two singles where it has none); the one-SNP ranges hold fewer
+    pairs than a round and run no pair item."""
+    d = data(name, "rate")
+    own = own_ranges(d.M)[k]
+    s = restated(name, own)
+    want, lists = pair_rounds_ab(d, s, {}, own=own)
+    if cu_count() == 256:
+        assert (want == "f4_colpair") == (k == 0), (want, lists)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["narrow_65k", "wide_100k"])
+def test_add_dom_column_pair_rounds_with_replayed_snps(data, name):
+    """Default flags: the rare variants (at N = 67 nearly every SNP) are replayed, so the pair items run their K loops
+    in the pair launch with the Gram tiles kept for the deferred epilogue (narrow_65k: its block pairs fit the 2^16
+    slots) or wait for the KC instantiation after the replay (wide_100k: they do not).  Bitwise f4_nc2_dom 0 only:
+    the replay arithmetic is held to the oracle in test_gpu_parity.py and test_gpu_colpair_dom.py."""
+    from nldsc_amd.engine import Engine
+    d, s = data(name, "rate"), restated(name)
+    rnd = 4 * cu_count()
+    want, round_items, lists = expected_pair_rounds(d, s, rnd)
+    out = {}
+    with Engine(0, options={"colpair_round_items": rnd}) as e:
+        e.load_bed_bytes(d.bed, d.M, N_ORG)
+        for on in (1, 0):
+            e.set_option("f4_nc2_dom", on)
+            out[on] = (e.run(d.w, MAF, STD_THR, 0.01, d.pos, flags=MODES["f4"]), e.timings())
+    (a, ta), (b, tb) = out[1], out[0]
+    assert (ta["band_kernel"], ta["band_round_items"], tb["band_kernel"], tb["band_round_items"]) == \
+        (want, round_items, "f4", 0), (ta, tb)
+    assert (ta["band_pair_items"], ta["band_pairs"], ta["band_pair_rest"]) == lists, (ta, lists)
+    assert ta["band_items"] == tb["band_items"] == s["items"] and ta["flop_issued"] == tb["flop_issued"] > 0
+    assert (s["items"] <= 1 << 16) == (name == "narrow_65k")
+    bitwise(a, b, f"{name} default flags: f4_nc2_dom 1 vs 0")
+    assert np.isfinite(a["l2"]).sum() > 0.5 * d.M
