@@ -173,10 +173,20 @@ def test_missing_rich_rows_keep_half(engine):
         assert_ld_close(got[m], orc, tol=tol_for(m), label=f"rare {m} vs oracle")
 
 
-def test_multi_slice_file_reader(engine, tmp_path):
-    """N = 315 599 (rows of 78 900 bytes), M = 900 (the expected file takes ~4 s of numpy per 1 000 rows): three
-    reader slices of 416, 416 and 68 rows, each on its own thread, slot and stream; the whole file and the row range
-    [200, 700) (two slices)."""
+SLICE_BYTES = 64 << 20  # ld_engine.cpp: the host and device loaders' staging slices
+
+
+def loader_slices(n_rows: int, row_bytes: int) -> list:
+    """Rows per staging slice of nldsc_engine_load_bed_host (row_bytes: the file's rows) and of
+    nldsc_engine_load_bed_device with a list (row_bytes: the compact rows): ~64 MiB of whole 32-SNP blocks."""
+    rows_per = max(32, SLICE_BYTES // row_bytes // 32 * 32)
+    return [min(rows_per, n_rows - r0) for r0 in range(0, n_rows, rows_per)]
+
+
+@pytest.fixture(scope="module")
+def long_rows(tmp_path_factory):
+    """N = 315 599 (rows of 78 900 bytes), M = 900, a random half of the individuals and the rows `plink --keep`
+    writes for them (~4 s of numpy), both as .bed files too."""
     N, M = 315_599, 900
     nb = (N + 3) // 4
     rng = np.random.default_rng(77)
@@ -191,7 +201,8 @@ def test_multi_slice_file_reader(engine, tmp_path):
     rows[:, -1] &= 0x3F
     idx = np.sort(rng.choice(N, N // 2, replace=False)).astype(np.int32)
     sub = subset_rows(rows, N, idx)
-    src, dst = tmp_path / "full.bed", tmp_path / "sub.bed"
+    d = tmp_path_factory.mktemp("long_rows")
+    src, dst = d / "full.bed", d / "sub.bed"
     with open(src, "wb") as fh:
         fh.write(b"\x6c\x1b\x01")
         fh.write(rows.tobytes())
@@ -199,7 +210,14 @@ def test_multi_slice_file_reader(engine, tmp_path):
         fh.write(b"\x6c\x1b\x01")
         fh.write(sub.tobytes())
     pos = np.cumsum(rng.exponential(0.02, M))
-    args = (1.0, 0.01, 1e-5, 1.0 / M)
+    rows.setflags(write=False)
+    return dict(N=N, M=M, rows=rows, idx=idx, src=src, dst=dst, pos=pos, args=(1.0, 0.01, 1e-5, 1.0 / M))
+
+
+def test_multi_slice_file_reader(engine, long_rows):
+    """The expected file takes ~4 s of numpy per 1 000 rows: three reader slices of 416, 416 and 68 rows, each on its
+    own thread, slot and stream; the whole file and the row range [200, 700) (two slices)."""
+    N, M, idx, src, dst, pos, args = (long_rows[k] for k in ("N", "M", "idx", "src", "dst", "pos", "args"))
     engine.set_keep(None)
     engine.load_bed_file(str(dst), M, len(idx))
     exp = engine.run(*args, pos, flags=STRICT)
@@ -218,6 +236,54 @@ def test_multi_slice_file_reader(engine, tmp_path):
     assert np.isfinite(exp["l2"]).sum() > M // 2
     assert_bitwise(got, exp, "file")
     assert_bitwise(got_range, exp_range, "file range")
+
+
+def test_multi_slice_host_loader(engine, long_rows):
+    """The host loader with the half list on the same rows: the 71 MB source goes up in two slices of 832 and 68 rows,
+    the second over both staging regions (source rows and compact rows) of the first.  Bitwise the file loader's
+    result, and the plain load's of the subset file."""
+    N, M, idx, src, dst, pos, args = (long_rows[k] for k in ("N", "M", "idx", "src", "dst", "pos", "args"))
+    assert loader_slices(M, (N + 3) // 4) == [832, 68]
+    engine.set_keep(None)
+    engine.load_bed_file(str(dst), M, len(idx))
+    exp = engine.run(*args, pos, flags=STRICT)
+    bed = np.fromfile(src, np.uint8)
+    try:
+        engine.set_keep(idx, N)
+        engine.load_bed_file(str(src), M, N)
+        by_file = engine.run(*args, pos)
+        engine.load_bed_bytes(bed, M, N)
+        assert engine.kept() == len(idx) and engine.n_snp == M
+        got = engine.run(*args, pos)
+    finally:
+        engine.set_keep(None)
+    assert_bitwise(got, by_file, "host loader vs file loader")
+    assert_bitwise(got, exp, "host loader vs the subset file")
+
+
+def test_multi_slice_device_loader_three_removed(engine, long_rows):
+    """The device loader slices by compact rows: with the first, a middle and the last individual removed they are
+    78 899 bytes, 832 + 68 rows again.  Bitwise the plain load of the subset bytes (a second ~4 s of numpy)."""
+    import torch
+    N, M, rows, src, pos, args = (long_rows[k] for k in ("N", "M", "rows", "src", "pos", "args"))
+    idx = np.setdiff1d(np.arange(N), [0, N // 2, N - 1]).astype(np.int32)
+    nb_img = (len(idx) + 3) // 4
+    assert nb_img == 78_899 and len(loader_slices(M, nb_img)) >= 2 and loader_slices(M, nb_img)[0] % 32 == 0
+    sub = subset_rows(rows, N, idx)
+    engine.set_keep(None)
+    engine.load_bed_bytes(np.concatenate([np.frombuffer(b"\x6c\x1b\x01", np.uint8), sub.reshape(-1)]), M, len(idx))
+    exp = engine.run(*args, pos, flags=STRICT)
+    dev = torch.from_numpy(np.fromfile(src, np.uint8)).cuda()  # (the rows start at +3: no alignment)
+    torch.cuda.synchronize()
+    try:
+        engine.set_keep(idx, N)
+        engine.load_bed_device(dev.data_ptr(), dev.numel(), M, N)
+        assert engine.kept() == len(idx) and engine.n_snp == M
+        got = engine.run(*args, pos)
+    finally:
+        engine.set_keep(None)
+    assert np.isfinite(exp["l2"]).sum() > M // 2
+    assert_bitwise(got, exp, "device loader, three removed")
 
 
 def test_index_validation_and_load_errors(engine, tmp_path):
