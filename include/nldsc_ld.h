@@ -266,6 +266,27 @@ int nldsc_engine_run_covar(nldsc_engine* e, const nldsc_ld_params* p, const doub
  * q_basis then has n_keep rows), in PLINK's sample order. */
 int nldsc_ld_calculate_covar(const nldsc_ld_params* p, const int32_t* keep_idx, int32_t n_keep, const double* q_basis,
                              int32_t n_covar, nldsc_ld_result* r, char* err, size_t errlen);
+/* Dominance-by-dominance LD scores (d-LDSC): nldsc_engine_run plus
+ *   l2dd[j] = 1 + sum over k of r2adj(R_j . R_k / n_org)
+ * with R the standardised dominance residual the run already forms for L2D (orthogonal to the additive coding).  The
+ * pair (j, k) counts exactly when it counts towards l2d_ws[j] (k in j's window and pointers, k passed MAF,
+ * rstd_k > std_thr) and j itself has rstd_j > std_thr; the self term 1 follows l2's; r2adj and n_org are l2d's.  l2dd[j]
+ * is NaN where l2[j] is NaN and where rstd_j <= std_thr (R_j is undefined).  Its neighbour count is l2d_ws[j]: no new
+ * count array.  l2dd: [n_snp] host array; the owned slice is written.
+ *   - The run implies NLDSC_FLAG_EXACT_RARE (closed-form vectors of rare variants: the new statistic has no reference
+ *     arithmetic to replay), so the seven ordinary arrays equal, bit for bit, those of a plain run with that flag,
+ *     and on data without replayed SNPs those of a default plain run.
+ *   - Every block pair goes through the K-split partial kernel with a ninth exact product (h . h), then through an
+ *     epilogue that adds the ordinary sums and the new one; the per-SNP sums are fixed-point, so l2dd is
+ *     bit-reproducible and does not depend on the schedule (batches: option annot_batch_items; K-split; owned ranges).
+ *   - NLDSC_E_ARG, with the reason in `err`: n_org >= 2^19 (the partial kernel takes unsegmented rows); a run that
+ *     does not take the exact fp4 path; NLDSC_FLAG_ADDITIVE_ONLY (no dominance residuals); l2dd NULL.  Host results
+ *     only; annotations, a pair table or covariates go in runs of their own.  Stateless: the next run is a plain one. */
+int nldsc_engine_run_domdom(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,
+                            nldsc_ld_result* r, double* l2dd, char* err, size_t errlen);
+/* One-shot: read `p->bedfile`, on the individuals keep_idx[n_keep] when keep_idx != NULL (nldsc_ld_calculate_keep). */
+int nldsc_ld_calculate_domdom(const nldsc_ld_params* p, const int32_t* keep_idx, int32_t n_keep, nldsc_ld_result* r,
+                              double* l2dd, char* err, size_t errlen);
 /* The projections of the last covariate run, for tests and tools: u, w [n_covar][n_snp] (U_j in the file's allele
  * coding, W_j), v, wd [n_snp] (v_j, w_j; 1 for SNPs that are not computed or have every call missing, whose U and W
  * are 0).  Any pointer may be NULL.  NLDSC_E_ARG when the engine's last covariate run did not complete. */
@@ -377,6 +398,11 @@ int nldsc_plan_band(const double* positions, const uint8_t* flags, int32_t n_snp
 int nldsc_annot_scale_exp(double max_abs);
 int nldsc_annot_plan_batches(int32_t n_items, int32_t n_it, int32_t n_cu, int32_t ksplit_ok, int32_t batch_items,
                              int32_t* batches, int32_t cap);
+/* The same for units (one K piece of one item) of unit_floats floats of Gram scratch under a cap of cap_bytes (0: the
+ * engine's 1 GiB): 8192 for the runs above, 9216 for a dom-dom run's nine tiles.  Every batch keeps
+ * items * pieces * unit_floats * 4 <= cap_bytes (a single item's pieces excepted: a batch holds one item at least). */
+int nldsc_plan_batches_unit(int32_t n_items, int32_t n_it, int32_t n_cu, int32_t ksplit_ok, int32_t batch_items,
+                            int64_t cap_bytes, int32_t unit_floats, int32_t* batches, int32_t cap);
 
 /* Host-only arithmetic of pairs runs (no GPU needed; the engine and its kernels use the same code).  _cell: the cell
  * of the dense count matrix that holds owned SNP g's entries against 32-SNP block nb, (g - own_begin) * wb +

@@ -68,13 +68,16 @@ def main():
                               "vector is residualised on the covariates before the correlations; implies PLINK sample "
                               "order (--strict-plink-order); not with --annot or --pairs-out", metavar="FILE",
               default=None)
+@click.option("--dom-dom", help="Also the dominance-by-dominance LD scores (d-LDSC): the column L2DD, the LD score of "
+                                "the dominance deviations with each other, after all other columns; not with --annot, "
+                                "--pairs-out, --covar or --additive-only", is_flag=True, default=False)
 @click.option("--additive-only", help="Skip the dominance terms (L2D = NaN)", is_flag=True, default=False)
 @click.option("--device", help="HIP device ordinal", type=int, default=None)
 @click.option("--quiet", help="No progress lines on stderr", is_flag=True, default=False)
 @click.option("--display", help="Display traceback", is_flag=True, default=False)
 @handle_exception
 def est_ld(bfile, out, ld_wind_kb, ld_wind_cm, maf_thr, std_thr, rsq_thr, extra, write_m, strict_plink_order,
-           keep, remove, annot, pairs_out, pairs_min_r2, covar, additive_only, device, quiet):
+           keep, remove, annot, pairs_out, pairs_min_r2, covar, dom_dom, additive_only, device, quiet):
     if sum(map(bool, [ld_wind_kb, ld_wind_cm])) != 1:
         raise RuntimeError("Please, specify exactly one --ld-wind option")
     elif ld_wind_kb:
@@ -89,12 +92,12 @@ def est_ld(bfile, out, ld_wind_kb, ld_wind_cm, maf_thr, std_thr, rsq_thr, extra,
         estimate_lds_genome(bfile, ld_wind=ld_wind, wind_metric=wind_metric, maf_thr=maf_thr, std_thr=std_thr,
                             rsq_thr=rsq_thr, out=out, extra=extra, write_m=write_m, flags=flags, device=device,
                             progress=not quiet, keep=keep, remove=remove, annot=annot, pairs_out=pairs_out,
-                            pairs_min_r2=pairs_min_r2, covar=covar)
+                            pairs_min_r2=pairs_min_r2, covar=covar, dom_dom=dom_dom)
         return
     estimate_lds(bfile, ld_wind=ld_wind, wind_metric=wind_metric, maf_thr=maf_thr, std_thr=std_thr,
                  rsq_thr=rsq_thr, out=out, extra=extra, summary=True, write_m=write_m, flags=flags, device=device,
                  progress=not quiet, keep=keep, remove=remove, annot=annot, pairs_out=pairs_out,
-                 pairs_min_r2=pairs_min_r2, covar=covar)
+                 pairs_min_r2=pairs_min_r2, covar=covar, dom_dom=dom_dom)
 
 
 @main.command("h2", help="(not part of this engine) heritability estimation")

@@ -37,7 +37,8 @@ EXPORTED = (
     "nldsc_engine_run_annot", "nldsc_ld_calculate_annot", "nldsc_annot_scale_exp", "nldsc_annot_plan_batches",
     "nldsc_engine_run_pairs", "nldsc_pairs_cell", "nldsc_pairs_window_blocks", "nldsc_pairs_split_ranges",
     "nldsc_engine_run_covar", "nldsc_ld_calculate_covar", "nldsc_engine_covar_projections",
-    "nldsc_engine_band_pair_items",
+    "nldsc_engine_band_pair_items", "nldsc_engine_run_domdom", "nldsc_ld_calculate_domdom",
+    "nldsc_plan_batches_unit",
 )
 MAX_ANNOT = 1024  # NLDSC_MAX_ANNOT
 MAX_COVAR = 64  # NLDSC_MAX_COVAR
@@ -159,6 +160,13 @@ def lib(path: str | None = None) -> ctypes.CDLL:
             L.nldsc_ld_calculate_covar.argtypes = [ctypes.POINTER(Params), vp, ctypes.c_int32, vp, ctypes.c_int32,
                                                    ctypes.POINTER(Result)] + c_err
             L.nldsc_engine_covar_projections.argtypes = [vp, vp, vp, vp, vp]
+        if hasattr(L, "nldsc_engine_run_domdom"):
+            L.nldsc_engine_run_domdom.argtypes = [vp, ctypes.POINTER(Params), ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.POINTER(Result), vp] + c_err
+            L.nldsc_ld_calculate_domdom.argtypes = [ctypes.POINTER(Params), vp, ctypes.c_int32,
+                                                    ctypes.POINTER(Result), vp] + c_err
+            L.nldsc_plan_batches_unit.argtypes = [ctypes.c_int32] * 5 + [ctypes.c_int64, ctypes.c_int32, vp,
+                                                                         ctypes.c_int32]
         L.nldsc_synth_bed_device.argtypes = [ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float,
                                              ctypes.c_uint64] + c_err
@@ -299,6 +307,23 @@ def annot_plan_batches(n_items: int, n_it: int, n_cu: int, ksplit_ok: bool = Tru
         raise ValueError(f"nldsc_annot_plan_batches error {k}")
     out = np.zeros((max(k, 1), 3), np.int32)
     assert lib().nldsc_annot_plan_batches(*args, out.ctypes.data, len(out)) == k
+    return out[:k]
+
+
+DD_UNIT_FLOATS = 9216  # Gram scratch of one unit of a dom-dom run: nine 32 x 32 fp32 tiles
+
+
+def plan_batches_unit(n_items: int, n_it: int, n_cu: int, unit_floats: int, ksplit_ok: bool = True,
+                      batch_items: int = 0, cap_bytes: int = 0) -> np.ndarray:
+    """annot_plan_batches for units of `unit_floats` floats of Gram scratch under `cap_bytes` (0: the engine's cap;
+    C ABI nldsc_plan_batches_unit; host only)."""
+    args = (int(n_items), int(n_it), int(n_cu), int(bool(ksplit_ok)), int(batch_items), int(cap_bytes),
+            int(unit_floats))
+    k = lib().nldsc_plan_batches_unit(*args, None, 0)
+    if k < 0:
+        raise ValueError(f"nldsc_plan_batches_unit error {k}")
+    out = np.zeros((max(k, 1), 3), np.int32)
+    assert lib().nldsc_plan_batches_unit(*args, out.ctypes.data, len(out)) == k
     return out[:k]
 
 

@@ -251,16 +251,16 @@ int annot_scale_exp(double max_abs) {
 
 double annot_scale(int e) { return std::ldexp(1.0, 44 - e); }
 
-int annot_batch_items(int want, size_t cap_bytes) {
-    const size_t hold = std::max<size_t>(1, cap_bytes / ((size_t)ANNOT_KSPLIT_MAX * 32768));
+int annot_batch_items(int want, size_t cap_bytes, size_t unit_bytes) {
+    const size_t hold = std::max<size_t>(1, cap_bytes / ((size_t)ANNOT_KSPLIT_MAX * std::max<size_t>(unit_bytes, 1)));
     const size_t n = want > 0 ? std::min<size_t>((size_t)want, hold) : hold;
     return (int)std::min<size_t>(n, (size_t)INT32_MAX);
 }
 
 std::vector<AnnotBatch> plan_annot_batches(int n_items, int n_it, int n_cu, bool ksplit_ok, int want,
-                                           size_t cap_bytes) {
+                                           size_t cap_bytes, size_t unit_bytes) {
     std::vector<AnnotBatch> out;
-    const int per = annot_batch_items(want, cap_bytes);
+    const int per = annot_batch_items(want, cap_bytes, unit_bytes);
     for (int first = 0; first < n_items; first += per) {
         const int n = std::min(per, n_items - first);
         int P = choose_ksplit(n, n_it, n_cu, ksplit_ok);
@@ -323,6 +323,19 @@ int nldsc_annot_plan_batches(int32_t n_items, int32_t n_it, int32_t n_cu, int32_
     if (n_items < 0 || n_it < 2 || n_cu <= 0 || batch_items < 0) return NLDSC_E_ARG;
     const std::vector<nldsc::AnnotBatch> b = nldsc::plan_annot_batches(n_items, n_it, n_cu, ksplit_ok != 0, batch_items,
                                                                        nldsc::ANNOT_GRAM_CAP_BYTES);
+    if ((int64_t)b.size() > (int64_t)cap || !batches) return (int)b.size();
+    for (size_t k = 0; k < b.size(); ++k) {
+        batches[3 * k] = b[k].first; batches[3 * k + 1] = b[k].n; batches[3 * k + 2] = b[k].ksplit;
+    }
+    return (int)b.size();
+}
+
+int nldsc_plan_batches_unit(int32_t n_items, int32_t n_it, int32_t n_cu, int32_t ksplit_ok, int32_t batch_items,
+                            int64_t cap_bytes, int32_t unit_floats, int32_t* batches, int32_t cap) {
+    if (n_items < 0 || n_it < 2 || n_cu <= 0 || batch_items < 0 || cap_bytes < 0 || unit_floats < 1) return NLDSC_E_ARG;
+    const std::vector<nldsc::AnnotBatch> b = nldsc::plan_annot_batches(
+        n_items, n_it, n_cu, ksplit_ok != 0, batch_items, cap_bytes > 0 ? (size_t)cap_bytes : nldsc::ANNOT_GRAM_CAP_BYTES,
+        (size_t)unit_floats * sizeof(float));
     if ((int64_t)b.size() > (int64_t)cap || !batches) return (int)b.size();
     for (size_t k = 0; k < b.size(); ++k) {
         batches[3 * k] = b[k].first; batches[3 * k + 1] = b[k].n; batches[3 * k + 2] = b[k].ksplit;

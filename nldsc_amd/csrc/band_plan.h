@@ -66,13 +66,15 @@ double annot_scale(int e);
 constexpr size_t ANNOT_GRAM_CAP_BYTES = (size_t)1 << 30;
 constexpr int ANNOT_KSPLIT_MAX = 8;  // choose_ksplit's largest P
 // Items of one batch: `want` (option "annot_batch_items") when positive, else all the cap holds at P =
-// ANNOT_KSPLIT_MAX; never above that, never below 1.
-int annot_batch_items(int want, size_t cap_bytes);
+// ANNOT_KSPLIT_MAX; never above that, never below 1.  unit_bytes: the Gram tiles of one unit (one K piece of one item):
+// 8 tiles of 4 KiB, or the 9 of a dom-dom run (ld_kernels.h DD_GRAM_UNIT).
+constexpr size_t GRAM_UNIT_BYTES = 32768;
+int annot_batch_items(int want, size_t cap_bytes, size_t unit_bytes = GRAM_UNIT_BYTES);
 // the batches of n_items single-block items, in order: items [first, first + n) K-split in ksplit pieces
 // (choose_ksplit of the batch; the Gram pieces are exact integers, so results do not depend on it)
 struct AnnotBatch { int first, n, ksplit; };
 std::vector<AnnotBatch> plan_annot_batches(int n_items, int n_it, int n_cu, bool ksplit_ok, int want,
-                                           size_t cap_bytes);
+                                           size_t cap_bytes, size_t unit_bytes = GRAM_UNIT_BYTES);
 
 // ---- pair tables (nldsc_engine_run_pairs): the dense count matrix and the owned ranges of a pair budget ----
 #ifdef __HIPCC__

@@ -332,6 +332,9 @@ struct nldsc_engine {
     std::vector<double> h_qt;
     int cov_batch_items = 0;
     int cov_n = 0, cov_M = 0;
+    // dom-dom runs (nldsc_engine_run_domdom): the fixed-point sums of r2adj(R_j . R_k) ([M]) and the finalized owned
+    // slice on its way to the host; their batches follow option "annot_batch_items"
+    DevBuf<double> l2dd_acc, l2dd_out;
     // the device table of a run (finish_table's input), kept for a split run between its two calls
     // (nldsc_engine_run_device_split / _finish: `pending`)
     struct SplitState {
@@ -1169,6 +1172,45 @@ int prepare_cov(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, co
     return NLDSC_OK;
 }
 
+// A dom-dom run's request (nldsc_engine_run_domdom): the caller's L2DD array, [n_snp]
+struct DomDomRun {
+    double* l2dd;
+};
+
+// The restrictions of a dom-dom run, each with its reason (those of an annotated run: the same partial kernel; and the
+// dominance residual must exist).  They need the parameters and the engine's options only, so they come before the
+// parameters are held against the loaded image.
+int check_dd(const nldsc_engine* e, const nldsc_ld_params* p, const DomDomRun& dd, bool other, char* err,
+             size_t errlen) {
+    if (other)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "dom-dom scores with annotations, a pair table or covariates in one run are not supported");
+    if (!dd.l2dd) return set_err(err, errlen, NLDSC_E_ARG, "l2dd is NULL");
+    if (p->flags & NLDSC_FLAG_ADDITIVE_ONLY)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "dom-dom scores need the dominance residuals: not with NLDSC_FLAG_ADDITIVE_ONLY");
+    if (p->n_org >= (1 << 19))
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "dom-dom runs need n_org < 2^19 (got %d): the K-split partial kernel takes unsegmented rows",
+                       p->n_org);
+    const RunShape s = run_shape(e, p, 0, p->n_snp, false);
+    if (s.path != 2)
+        return set_err(err, errlen, NLDSC_E_ARG,
+                       "dom-dom runs take the exact fp4 path only: this run's flags or the band_mode option select %s",
+                       s.path == 0 ? "fp32" : "exact int8");
+    return NLDSC_OK;
+}
+
+// the accumulator and the owned slice's landing buffer of a dom-dom run, the accumulator zeroed (main stream, before
+// the prologue)
+int prepare_dd(nldsc_engine* e, const RunShape& s, char* err, size_t errlen) {
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(e->l2dd_acc.ensure((size_t)s.M));
+    HIPCHK(e->l2dd_out.ensure((size_t)std::max(s.own_end - s.own_begin, 1)));
+    HIPCHK(hipMemsetAsync(e->l2dd_acc.p, 0, sizeof(double) * (size_t)s.M, e->stream));
+    return NLDSC_OK;
+}
+
 // the work buffers of a run, sized (allocation happens on the first run of a size; the enqueue phases allocate only
 // what depends on the schedule's counts)
 int ensure_run_buffers(nldsc_engine* e, const RunShape& s, const PlanMode& m, char* err, size_t errlen) {
@@ -1636,6 +1678,49 @@ int enqueue_band_cov(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& 
     return NLDSC_OK;
 }
 
+// The band of a dom-dom run (ev[3] .. ev[4]): the single-block items in batches (as an annotated band's, sized for
+// units of nine tiles) through the K-split partial kernel with the h.h product and the dom-dom epilogue
+// (launch_band_f4_dd); no replay to wait for (the run takes the closed-form vectors); then the issued-product count
+// as enqueue_band queues it, one more product per item.
+int enqueue_band_dd(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m,
+                    const Schedule& sc, char* err, size_t errlen) {
+    hipStream_t st = e->stream, cs = e->copy_stream;
+    const int n_items = sc.n_items;
+    HIPCHK(hipEventRecord(e->ev[3], st));
+    const size_t unit = nldsc::DD_GRAM_UNIT;
+    const std::vector<nldsc::AnnotBatch> batches = nldsc::plan_annot_batches(
+        n_items, s.n_it, e->n_cu, e->ksplit_ok, e->annot_batch_items, nldsc::ANNOT_GRAM_CAP_BYTES, unit * sizeof(float));
+    size_t units = 0;
+    int p_max = 1;
+    for (const nldsc::AnnotBatch& b : batches) {
+        units = std::max(units, (size_t)b.n * (size_t)b.ksplit);
+        p_max = std::max(p_max, b.ksplit);
+    }
+    e->n_band_items = n_items;
+    e->last_ksplit = p_max;
+    e->last_round_items = 0;
+    e->last_pair_items[0] = e->last_pair_items[1] = e->last_pair_items[2] = 0;
+    e->last_tail_ksplit = 1;
+    e->last_band_kernel = NLDSC_BAND_F4_KSPLIT;
+    HIPCHK(e->gram.ensure(std::max<size_t>(units, 1) * unit));
+    const nldsc::BandArgs a = fill_band_args(e, p, s, m);
+    for (const nldsc::AnnotBatch& b : batches)
+        HIPCHK(nldsc::launch_band_f4_dd(a, b.ksplit, e->items.p + b.first, b.n, e->gram.p, e->l2dd_acc.p));
+    e->last_path = s.path;
+    HIPCHK(hipEventRecord(e->ev[4], st));
+    HIPCHK(e->sums.ensure(3));
+    HIPCHK(e->h_sums.ensure(3 * sizeof(unsigned long long)));
+    HIPCHK(hipStreamWaitEvent(cs, e->ev[3], 0));
+    HIPCHK(hipMemsetAsync(e->sums.p + 2, 0, sizeof(unsigned long long), cs));
+    HIPCHK(nldsc::launch_issued_products(e->items.p, n_items, nullptr, 0, m.gpu_plan ? e->plan_rows.p : nullptr,
+                                         e->blk_miss.p, s.nblk, s.path, s.dom, 0, m.route_shift, e->sums.p + 2, cs,
+                                         true));
+    HIPCHK(hipMemcpyAsync(e->h_sums.p + 2 * sizeof(unsigned long long), e->sums.p + 2, sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipEventRecord(e->ev_issued, cs));
+    return NLDSC_OK;
+}
+
 // A pairs run's request (nldsc_engine_run_pairs): the filter, the caller's CSR arrays and their capacity; `emitted`:
 // the table is in the device buffers, to be copied out once the stream is drained
 struct PairsRun {
@@ -1755,7 +1840,8 @@ int enqueue_band_pairs(nldsc_engine* e, const nldsc_ld_params* p, const RunShape
 // count on the side stream (ev_issued).
 int enqueue_band(nldsc_engine* e, const nldsc_ld_params* p, const RunShape& s, const PlanMode& m, const Schedule& sc,
                  char* err, size_t errlen, const AnnotRun* an = nullptr, PairsRun* pr = nullptr,
-                 const CovRun* cv = nullptr) {
+                 const CovRun* cv = nullptr, const DomDomRun* dd = nullptr) {
+    if (dd) return enqueue_band_dd(e, p, s, m, sc, err, errlen);
     if (cv) return enqueue_band_cov(e, p, s, m, sc, *cv, err, errlen);
     if (an) return enqueue_band_annot(e, p, s, m, sc, *an, err, errlen);
     if (pr) return enqueue_band_pairs(e, p, s, m, sc, *pr, err, errlen);
@@ -1986,9 +2072,12 @@ int finish_host(nldsc_engine* e, const RunShape& s, const HostOut& o, double* sw
 int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end, nldsc_ld_result* r,
              double* table_dev, int32_t width, char* err, size_t errlen, long long* export_dev = nullptr,
              int32_t export_cap = 0, int32_t* export_n = nullptr, const AnnotRun* an = nullptr,
-             PairsRun* pr = nullptr, const CovRun* cv = nullptr) {
+             PairsRun* pr = nullptr, const CovRun* cv = nullptr, const DomDomRun* dd = nullptr) {
     const bool split = export_n != nullptr;
-    int rc = check_run_args(e, p, own_begin, own_end, r, table_dev, width, split, export_dev, export_cap, err, errlen);
+    int rc = 0;
+    if (dd && e && p && (rc = check_dd(e, p, *dd, an != nullptr || pr != nullptr || cv != nullptr, err, errlen)))
+        return rc;
+    rc = check_run_args(e, p, own_begin, own_end, r, table_dev, width, split, export_dev, export_cap, err, errlen);
     if (rc) return rc;
     if (cv && (rc = prepare_cov(e, p, run_shape(e, p, own_begin, own_end, split), *cv, an != nullptr || pr != nullptr,
                                 err, errlen)))
@@ -2003,8 +2092,9 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     e->last_direct = -1;
     if (!table_dev && (rc = resolve_host_out(e, r, own_begin, own_end, &out, err, errlen))) return rc;
     const RunShape s = run_shape(e, p, own_begin, own_end, split);
-    const PlanMode m = plan_mode(e, p, s, an != nullptr || pr != nullptr || cv != nullptr);
+    const PlanMode m = plan_mode(e, p, s, an != nullptr || pr != nullptr || cv != nullptr || dd != nullptr);
     if ((rc = ensure_run_buffers(e, s, m, err, errlen))) return rc;
+    if (dd && (rc = prepare_dd(e, s, err, errlen))) return rc;
 
     const auto t_start = Clock::now();
     if ((rc = enqueue_prologue(e, p, s, m, err, errlen, cv))) return rc;
@@ -2015,7 +2105,10 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
     if (rc) return rc;
     // (l2_acc, l2d_acc and ws_acc were zeroed by snp_stats_kernel)
     const auto t_host1 = Clock::now();
-    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen, an, pr, cv))) return rc;
+    if ((rc = enqueue_band(e, p, s, m, sc, err, errlen, an, pr, cv, dd))) return rc;
+    if (dd)  // L2DD of the owned slice, finalized beside the ordinary scores (.. ev[5])
+        HIPCHK(nldsc::launch_finalize_dd(e->Lw.p, e->l2dd_acc.p, e->ws_acc.p, e->sflags.p, s.M, own_begin, own_end,
+                                         e->l2dd_out.p, e->stream));
     if (an) {  // the per-annotation scores of the owned slice, finalized beside the ordinary ones (.. ev[5])
         double* o2 = e->annot_out.p;
         HIPCHK(nldsc::launch_finalize_annot(e->Lw.p, e->ws_acc.p, annot_args(e, s, *an), s.M, own_begin, own_end, s.dom,
@@ -2045,6 +2138,9 @@ int run_impl(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32
             HIPCHK(hipMemcpy2D(an->l2d + own_begin, sizeof(double) * (size_t)s.M, e->annot_out.p + (size_t)an->n * n_own,
                                row, row, (size_t)an->n, hipMemcpyDeviceToHost));
     }
+    if (dd)  // (the stream is drained) the owned slice into the caller's array
+        HIPCHK(hipMemcpy(dd->l2dd + own_begin, e->l2dd_out.p, sizeof(double) * (size_t)(own_end - own_begin),
+                         hipMemcpyDeviceToHost));
     if (pr && pr->emitted) {  // (the stream is drained) the table into the caller's arrays
         const size_t T = (size_t)*pr->n_pairs;
         HIPCHK(hipMemcpy(pr->k, e->pairs_k.p, sizeof(int32_t) * T, hipMemcpyDeviceToHost));
@@ -2115,6 +2211,17 @@ int nldsc_engine_run_covar(nldsc_engine* e, const nldsc_ld_params* p, const doub
     q.flags |= NLDSC_FLAG_EXACT_RARE;
     const CovRun cv = {q_basis, n_covar};
     return run_impl(e, &q, own_begin, own_end, r, nullptr, 0, err, errlen, nullptr, 0, nullptr, nullptr, nullptr, &cv);
+}
+
+int nldsc_engine_run_domdom(nldsc_engine* e, const nldsc_ld_params* p, int32_t own_begin, int32_t own_end,
+                            nldsc_ld_result* r, double* l2dd, char* err, size_t errlen) {
+    if (!r || !p) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
+    // the closed-form vectors of rare variants: the new statistic has no reference arithmetic to replay
+    nldsc_ld_params q = *p;
+    q.flags |= NLDSC_FLAG_EXACT_RARE;
+    const DomDomRun dd = {l2dd};
+    return run_impl(e, &q, own_begin, own_end, r, nullptr, 0, err, errlen, nullptr, 0, nullptr, nullptr, nullptr,
+                    nullptr, &dd);
 }
 
 int nldsc_engine_covar_projections(nldsc_engine* e, double* u, double* w, double* v, double* wd) {
@@ -2264,6 +2371,23 @@ int nldsc_ld_calculate_covar(const nldsc_ld_params* p, const int32_t* keep_idx, 
         q.n_org = e->n_org;  // the kept count (p->n_org without a list)
         q.flags |= NLDSC_FLAG_STRICT_PLINK_ORDER;  // (q_basis rows are .fam lines)
         rc = nldsc_engine_run_covar(e, &q, q_basis, n_covar, 0, p->n_snp, r, err, errlen);
+    }
+    nldsc_engine_destroy(e);
+    return rc;
+}
+
+int nldsc_ld_calculate_domdom(const nldsc_ld_params* p, const int32_t* keep_idx, int32_t n_keep, nldsc_ld_result* r,
+                              double* l2dd, char* err, size_t errlen) {
+    if (!p || !r || !p->bedfile) return set_err(err, errlen, NLDSC_E_ARG, "NULL argument");
+    nldsc_engine* e = nullptr;
+    int rc = nldsc_engine_create(p->device, &e, err, errlen);
+    if (rc) return rc;
+    if (keep_idx) rc = nldsc_engine_set_keep(e, keep_idx, n_keep, p->n_org, err, errlen);
+    if (!rc) rc = nldsc_engine_load_bed_file(e, p->bedfile, p->n_snp, p->n_org, err, errlen);
+    if (!rc) {
+        nldsc_ld_params q = *p;
+        q.n_org = e->n_org;  // the kept count (p->n_org without a list)
+        rc = nldsc_engine_run_domdom(e, &q, 0, p->n_snp, r, l2dd, err, errlen);
     }
     nldsc_engine_destroy(e);
     return rc;

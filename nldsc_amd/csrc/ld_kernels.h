@@ -203,6 +203,18 @@ hipError_t launch_covar_project(const uint8_t* img, int row_bytes, int n_snp, in
 // (a.blk_rep must be nullptr: no replay in a covariate run)
 hipError_t launch_band_f4_cov(const BandArgs& a, const CovArgs& cv, int P, const int4* items, int n_items,
                               float* gram);
+// Dominance-by-dominance LD scores (nldsc_engine_run_domdom).  One batch of a dom-dom band: band_f4_part_kernel with
+// the ninth product h.h (P pieces per item, all items) into `gram` (n_items * P * DD_GRAM_UNIT floats), then
+// band_f4_epi_dd_kernel — the ordinary per-SNP sums as band_f4_epi_kernel adds them plus the sums of r2adj(R_j . R_k)
+// into l2dd_acc ([n_snp], 2^-44 fixed point, zeroed before the band; non-finite sums set bit 4 of the nanf row of
+// ws_acc).  Add+dom runs only, single-block items (I, J, 1, 0), unsegmented rows, no routing; a.blk_rep must be
+// nullptr (no replay in a dom-dom run).
+constexpr size_t DD_GRAM_UNIT = 9 * 1024;
+hipError_t launch_band_f4_dd(const BandArgs& a, int P, const int4* items, int n_items, float* gram, double* l2dd_acc);
+// out[k] = L2DD of SNP own_lo + k (device memory, own_hi - own_lo doubles): 1 + the sum, NaN where L2 is NaN and where
+// the SNP's residual did not pass (sflags bit 1)
+hipError_t launch_finalize_dd(const int* Lw, const double* l2dd_acc, const int* ws_acc, const uint8_t* sflags,
+                              int n_snp, int own_lo, int own_hi, double* out, hipStream_t st);
 // Pair tables (nldsc_engine_run_pairs): the dense count matrix cnt[own_n][Wb] (band_plan.h pairs_cell; zeroed before
 // the count pass, turned into each row's exclusive offsets by launch_pairs_row_scan), and for the emit pass the
 // table's row_ptr (own_n + 1, device memory), its n_pairs entries k / r / rd; min_r2: NaN = no filter; flip (or
@@ -267,7 +279,8 @@ hipError_t launch_finalize_out(const int* Lw, const double* l2_acc, const double
 // blk_miss may be nullptr for kinds 0 and 1.  out[0] += the count (zeroed before)
 hipError_t launch_issued_products(const int4* items, int n_items, const int4* items2, int n_items2, const int2* rows,
                                  const uint8_t* blk_miss, int nblk, int kind, bool dom, int routed, int route_shift,
-                                 unsigned long long* out, hipStream_t st);
+                                 unsigned long long* out, hipStream_t st, bool hh = false);
+// (hh: the items of a dom-dom run, one more product — h.h — per fp4 single-block item)
 // the single-block items no super-item kernel takes (routing of 2^route_shift-block super-items), in their order, to
 // `out`; *total = their count (device); chunk_counts: ceil(n_items / 256) ints of scratch
 hipError_t launch_compact_items(const int4* items, int n_items, const uint8_t* blk_miss, int route_shift, int nblk,

@@ -2034,10 +2034,13 @@ __device__ __forceinline__ f32x16v mfma_f4(const i32x4& a, const i32x4& b, const
 // of 2^16 move to packed 16-bit counters (additive-only), exact while every entry is <= 16N < 2^31.
 // PART: K-split partial mode (small launches, see band_f4_part_kernel): run chunks [t_lo, t_hi) only and store
 // the 8 fp32 Gram tiles to `part` (exact integers) instead of running the epilogue.
+// HH (PART only; dom-dom runs, band_f4_part_kernel<DOM, true>): a ninth product h.h, stored as the unit's ninth tile.
+// h is 0 on missing calls and padding, so it needs no m correction and is issued whatever RM / CM are; each operand
+// carries its own block scale (H_SCALE), so the entry is the plain count of slots with h set in both SNPs.
 // the chunk loads of the K loop stay where they are written (issued two K steps before their data is decoded): left to
 // itself the scheduler sank them to within ~10 MFMAs of their use, behind an s_waitcnt vmcnt(0)
 #define NLDSC_LOAD_FENCE() __builtin_amdgcn_sched_barrier(0)
-template <bool DOM, int NC, bool DIAG0, int SEG, bool KC, bool PART = false>
+template <bool DOM, int NC, bool DIAG0, int SEG, bool KC, bool PART = false, bool HH = false>
 __device__ __forceinline__ void band_f4_body(BandI8Lds& sh, const int4 it, const uint32_t* __restrict__ geno,
                                              int pitch_words, int n_it, const SnpConst* __restrict__ cst,
                                              const double* __restrict__ pos, const int* __restrict__ Lw,
@@ -2060,6 +2063,8 @@ __device__ __forceinline__ void band_f4_body(BandI8Lds& sh, const int4 it, const
     f32x16v gxx[NC], gxo[NC], gox[NC], goo[NC], gxh[NC], goh[NC], ghx[NC], gho[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) gxx[c] = gxo[c] = gox[c] = goo[c] = gxh[c] = goh[c] = ghx[c] = gho[c] = f32x16v{};
+    static_assert(!HH || (PART && DOM), "the h.h product: the K-split partial kernel of an add+dom run");
+    [[maybe_unused]] std::conditional_t<HH, f32x16v, char> ghh{};
     const uint4* rowp = reinterpret_cast<const uint4*>(geno) + row_u4(I * 32 + i, pitch_words) + h;
     const uint4* colp[NC];
 #pragma unroll
@@ -2081,17 +2086,18 @@ __device__ __forceinline__ void band_f4_body(BandI8Lds& sh, const int4 it, const
             if (RM && CM) goo[c] = mfma_f4(a.o, b[c].o, goo[c]);
             if (DOM && RM) goh[c] = mfma_f4<E8M0_ONE, H_SCALE<CM>>(a.o, b[c].h, goh[c]);
             if (DOM && CM && !(DIAG0 && c == 0)) gho[c] = mfma_f4<H_SCALE<RM>, E8M0_ONE>(a.h, b[c].o, gho[c]);
+            if constexpr (HH) ghh = mfma_f4<H_SCALE<RM>, H_SCALE<CM>>(a.h, b[c].h, ghh);
         }
         // full 8-product steps: F4_VPM VALU after each MFMA; otherwise (additive-only items, missing-free
         // blocks) the decode is spread evenly over the MFMAs there are (additive-only C2: -6.6 % band time)
         if constexpr (RM && CM && DOM) {
 #pragma unroll
-            for (int m = 0; m < 8 * NC; ++m) {
+            for (int m = 0; m < (8 + HH) * NC; ++m) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x002, NC == 1 ? F4_VPM : 4, 0);
             }
         } else {
-            constexpr int n_mfma = NC * (1 + CM + RM + (RM && CM) + (DOM ? 2 + RM + CM : 0));
+            constexpr int n_mfma = NC * (1 + CM + RM + (RM && CM) + (DOM ? 2 + RM + CM : 0) + HH);
             constexpr int n_valu = (RM ? 9 : 6) * 2 + NC * (CM ? 9 : 6) * 2;  // the row strip decoded once
 #pragma unroll
             for (int m = 0; m < n_mfma; ++m) {
@@ -2168,6 +2174,11 @@ __device__ __forceinline__ void band_f4_body(BandI8Lds& sh, const int4 it, const
             const f32x16v v = *tiles[t];
 #pragma unroll
             for (int q = 0; q < 4; ++q) dst[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+        }
+        if constexpr (HH) {
+            float4* dst = reinterpret_cast<float4*>(part + 8 * 1024 + lane * 16);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) dst[q] = make_float4(ghh[4 * q], ghh[4 * q + 1], ghh[4 * q + 2], ghh[4 * q + 3]);
         }
         return;
     } else if constexpr (SEG == 0) {
@@ -2750,7 +2761,7 @@ __global__ void __launch_bounds__(COMPACT_CHUNK) compact_scatter_kernel(const in
 __global__ void issued_products_kernel(const int4* __restrict__ items, int n_items, const int4* __restrict__ items2,
                                        int n_items2, const int2* __restrict__ rows, const uint8_t* __restrict__ blk_miss,
                                        int nblk, int kind, int dom, int routed, int route_shift,
-                                       unsigned long long* __restrict__ out) {
+                                       unsigned long long* __restrict__ out, int hh) {
     // routed bit 0: single items the routing sends to a super-item kernel are not counted here (an uncompacted
     // list); bit 1: super-items count only when routed to their kernel
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2763,7 +2774,7 @@ __global__ void issued_products_kernel(const int4* __restrict__ items, int n_ite
                 const int J = it.y + c;
                 if ((routed & 1) && routed_item(blk_miss, route_shift, it.x, J, nblk)) continue;
                 const int rm = blk_miss[it.x] != 0, cm = blk_miss[J] != 0, nd = it.x != J;
-                n += 1 + cm + rm * nd + rm * cm + (dom ? 1 + nd + rm + cm * nd : 0);
+                n += 1 + cm + rm * nd + rm * cm + (dom ? 1 + nd + rm + cm * nd : 0) + hh;  // (hh: a dom-dom run's h.h)
             }
         } else if (kind == 1) {
             n = 4 + (dom ? (diag ? 2 : 4) : 0);
@@ -2865,7 +2876,8 @@ __global__ void plan_qemit_kernel(const int2* __restrict__ rows2, int nblk2, con
 // (even-aligned) and stores its 8 Gram tiles (32 KiB) to gram + u * 8192; band_f4_epi_kernel adds the P partial
 // tiles of each item in piece order — integers below 2^24 (N < 2^19), so the fp32 sums are exact and equal to the
 // single-pass Gram — and runs the usual epilogue.
-template <bool DOM>
+// HH (dom-dom runs): the ninth product h.h as the unit's ninth tile, units of DD_GRAM_UNIT = 9 216 floats.
+template <bool DOM, bool HH = false>
 __global__ void __launch_bounds__(64, 2) band_f4_part_kernel(const uint32_t* __restrict__ geno, int pitch_words,
                                                            int n_it, const SnpConst* __restrict__ cst,
                                                            const int4* __restrict__ items,
@@ -2882,10 +2894,11 @@ __global__ void __launch_bounds__(64, 2) band_f4_part_kernel(const uint32_t* __r
     if (blk_miss != nullptr && routed_item(blk_miss, route_shift, it.x, it.y, (n_snp + 31) >> 5)) return;
     const int t_lo = (int)(((long long)piece * n_it / P) & ~1LL);
     const int t_hi = piece == P - 1 ? n_it : (int)(((long long)(piece + 1) * n_it / P) & ~1LL);
-    float* part = gram + (size_t)u * 8192;
+    float* part = gram + (size_t)u * (HH ? DD_GRAM_UNIT : 8192);
 #define NLDSC_BODY(DIAG_)                                                                                             \
-    band_f4_body<DOM, 1, DIAG_, 0, false, true>(sh, it, geno, pitch_words, n_it, cst, pos, Lw, Rw, sflags, n_snp,     \
-                                                0.0, 0.0, 0.0, 0, 0, nullptr, nullptr, nullptr, tr, t_lo, t_hi, part)
+    band_f4_body<DOM, 1, DIAG_, 0, false, true, HH>(sh, it, geno, pitch_words, n_it, cst, pos, Lw, Rw, sflags, n_snp, \
+                                                    0.0, 0.0, 0.0, 0, 0, nullptr, nullptr, nullptr, tr, t_lo, t_hi,   \
+                                                    part)
     if (it.y == it.x) NLDSC_BODY(true); else NLDSC_BODY(false);
 #undef NLDSC_BODY
 }
@@ -2893,8 +2906,10 @@ __global__ void __launch_bounds__(64, 2) band_f4_part_kernel(const uint32_t* __r
 // How every K-split epilogue kernel (one wave per item) starts on item `it` = items[blockIdx.x]: the 64 slots (the
 // SNPs of block it.x, then of it.y) to info / scst; the item's P partial Gram tiles summed in piece order into g8
 // (x.x, x.m, m.x, m.m, x.h, m.h, h.x, h.m); a diagonal item's m.x = (x.m)^T through `tr` (32 x 33 floats).
-// Returns the lane's own slot.
-__device__ __forceinline__ SnpSlot load_split_item(SnpSlot* info, SnpConst* scst, float* tr, f32x16v (&g8)[8],
+// Returns the lane's own slot.  NT = 9 (dom-dom runs): units of 9 tiles, the ninth h.h, which is symmetric on a
+// diagonal item as it stands.
+template <int NT>
+__device__ __forceinline__ SnpSlot load_split_item(SnpSlot* info, SnpConst* scst, float* tr, f32x16v (&g8)[NT],
                                                    const int4 it, const SnpConst* __restrict__ cst,
                                                    const double* __restrict__ pos, const int* __restrict__ Lw,
                                                    const int* __restrict__ Rw, const uint8_t* __restrict__ sflags,
@@ -2905,12 +2920,13 @@ __device__ __forceinline__ SnpSlot load_split_item(SnpSlot* info, SnpConst* scst
     info[lane] = slot;
     scst[lane] = cst[g];
 #pragma unroll
-    for (int t = 0; t < 8; ++t) g8[t] = f32x16v{};
-    const float* src = gram + (size_t)blockIdx.x * P * 8192 + lane * 16;
+    for (int t = 0; t < NT; ++t) g8[t] = f32x16v{};
+    static_assert(NT == 8 || NT == 9, "8 tiles, or 9 with h.h");
+    const float* src = gram + (size_t)blockIdx.x * P * (NT * 1024) + lane * 16;
     for (int p = 0; p < P; ++p)
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const float4* q = reinterpret_cast<const float4*>(src + (size_t)p * 8192 + t * 1024);
+        for (int t = 0; t < NT; ++t) {
+            const float4* q = reinterpret_cast<const float4*>(src + (size_t)p * (NT * 1024) + t * 1024);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float4 v = q[k];
@@ -2956,6 +2972,131 @@ __global__ void __launch_bounds__(64, 2) band_f4_epi_kernel(const SnpConst* __re
     pair_epilogue<DOM, f32x16v, true, KC>(sh.info, sh.cst, 0, 32, diag, i, h, g8[0], g8[1], g8[2], g8[3], g8[4], g8[5],
                                           g8[6], g8[7], ld_wind, n_org, rsq_thr, n_org, own_lo, own_hi, n_snp, l2_acc,
                                           l2d_acc, ws_acc);
+}
+
+// ---- dominance-by-dominance LD scores: L2DD_j = 1 + sum_k r2adj(R_j . R_k / N) (nldsc_engine_run_domdom) ----
+// A dom-dom run sends every block pair through band_f4_part_kernel<true, true> (nine exact Gram tiles to memory, the
+// ninth h.h) and then through band_f4_epi_dd_kernel: pair_epilogue on the first eight tiles as band_f4_epi_kernel
+// runs it (the seven ordinary arrays are a plain run's by construction), then dd_epilogue for the new sum.  With
+// R_i = (2 h_i - beta_i x_i - c_i o_i) is_i over the individual slots,
+//   R_i . R_j = (4 h.h - 2 beta_j h.x - 2 c_j h.o - 2 beta_i x.h + beta_i beta_j x.x + beta_i c_j x.o
+//                - 2 c_i o.h + c_i beta_j o.x + c_i c_j o.o) is_i is_j      (row SNP's plane first in every product)
+// from the nine tiles in the missing basis, as pair_epilogue recovers the x and o products.  The pair (j, k) counts
+// towards L2DD_j where it counts towards WSD_j (j's window scan covers k, k passed MAF and has rstd_k > std_thr:
+// nij && flag bit 1 of k) and j itself has rstd_j > std_thr; the dot is symmetric, so one evaluation serves the row
+// SNP (nij) and, off the diagonal, the column SNP (nji).  The sums are reduced as the plain ones (reduce_rows4 /
+// xlane<32>) and go to l2dd_acc in acc_fixed's 2^-44 fixed point (non-finite: nanf bit 4): order-independent,
+// whatever the batch, the K-split factor and the owned range.  No KC form: a dom-dom run takes the closed-form
+// vectors of rare variants (NLDSC_FLAG_EXACT_RARE), so ka = kr = 0 everywhere.
+__device__ __forceinline__ void flush_slot_dd(const SnpSlot& si, const SlotSum& v, int own_lo, int own_hi, int n_snp,
+                                              double* l2dd_acc, int* ws_acc) {
+    const int g = si.g;
+    if (v.cnt == 0 || g < own_lo || g >= own_hi || g >= n_snp) return;
+    acc_fixed(&l2dd_acc[g], &ws_acc[3 * (size_t)n_snp + g], 4, v.l2);
+}
+
+// g: x.x, x.m, m.x, m.m, x.h, m.h, h.x, h.m (on a diagonal item h.x and h.m already transposed from x.h and m.h), h.h
+__device__ __forceinline__ void dd_epilogue(const SnpSlot* info, const SnpConst* cst, bool diag, int i, int h,
+                                            const f32x16v (&g)[9], double ld_wind, double n_org, int own_lo,
+                                            int own_hi, int n_snp, double* __restrict__ l2dd_acc,
+                                            int* __restrict__ ws_acc) {
+    const R2Adj r2adj(n_org);
+    const int sj = 32 + i;
+    const SnpSlot cj = info[sj];
+    const SnpConst kj = cst[sj];
+    const bool rpj = (cj.fl & 2) != 0;
+    SlotSum col = {0.0, 0.0, 0}, mine = {0.0, 0.0, 0};
+    int my_row = -1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        SlotSum rowv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int r = 4 * q + k;
+            const int si = k + 8 * q + 4 * h;
+            const SnpSlot ci = info[si];
+            const bool rp = rpj && (ci.fl & 2) != 0;
+            const PairNeed need = pair_need(ci, cj, diag, ld_wind);
+            SlotSum rv = {0.0, 0.0, 0};
+            if (rp && (need.nij || need.nji)) {
+                const SnpConst ki = cst[si];
+                const double mm = (double)g[3][r];
+                const double xx = 0.25 * ((double)g[0][r] - (double)g[1][r] - (double)g[2][r] + mm);
+                const double xo = ki.X - 0.5 * ((double)g[1][r] - mm);
+                const double ox = kj.X - 0.5 * ((double)g[2][r] - mm);
+                const double oo = ki.Ob + kj.Ob - n_org + mm;
+                const double xh = 0.5 * ((double)g[4][r] - (double)g[5][r]);
+                const double oh = kj.H - (double)g[5][r];
+                const double hx = 0.5 * ((double)g[6][r] - (double)g[7][r]);
+                const double ho = ki.H - (double)g[7][r];
+                const double hh = (double)g[8][r];
+                const double dd = (4.0 * hh - 2.0 * (kj.beta * hx + kj.c * ho) -
+                                   ki.beta * (2.0 * xh - kj.beta * xx - kj.c * xo) -
+                                   ki.c * (2.0 * oh - kj.beta * ox - kj.c * oo)) * (ki.is * kj.is);
+                const double r2 = r2adj(dd);
+                if (need.nij) { rv.l2 = r2; rv.cnt = 1; }
+                if (need.nji) { col.l2 += r2; col.cnt += 1; }
+            }
+            rowv[k] = rv;
+        }
+        const SlotSum t = reduce_rows4(rowv, i);  // lanes i >> 3 == k: row k + 8q + 4h
+        if ((i & 7) == q) {
+            mine = t;
+            my_row = (i >> 3) + 8 * q + 4 * h;
+        }
+    }
+    col = col + xlane<32>(col);
+    if (my_row >= 0) flush_slot_dd(info[my_row], mine, own_lo, own_hi, n_snp, l2dd_acc, ws_acc);
+    if (h == 0) flush_slot_dd(cj, col, own_lo, own_hi, n_snp, l2dd_acc, ws_acc);
+}
+
+// (no waves-per-SIMD bound: nine fp32 tiles beside the fp64 epilogue need more than 256 registers)
+template <bool DOM>
+__global__ void __launch_bounds__(64) band_f4_epi_dd_kernel(
+    const SnpConst* __restrict__ cst, const int4* __restrict__ items, const double* __restrict__ pos,
+    const int* __restrict__ Lw, const int* __restrict__ Rw, const uint8_t* __restrict__ sflags, int n_snp,
+    double ld_wind, double n_org, double rsq_thr, int own_lo, int own_hi, double* __restrict__ l2_acc,
+    double* __restrict__ l2d_acc, int* __restrict__ ws_acc, int P, const float* __restrict__ gram,
+    double* __restrict__ l2dd_acc) {
+    static_assert(DOM, "dom-dom runs are add+dom runs");
+    __shared__ SlotLds<64> sh;
+    __shared__ float tr[32 * 33];
+    const int4 it = items[blockIdx.x];
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    f32x16v g9[9];
+    load_split_item(sh.info, sh.cst, tr, g9, it, cst, pos, Lw, Rw, sflags, n_snp, P, gram);
+    const bool diag = it.x == it.y;
+    pair_epilogue<DOM, f32x16v, true, false>(sh.info, sh.cst, 0, 32, diag, i, h, g9[0], g9[1], g9[2], g9[3], g9[4],
+                                             g9[5], g9[6], g9[7], ld_wind, n_org, rsq_thr, n_org, own_lo, own_hi,
+                                             n_snp, l2_acc, l2d_acc, ws_acc);
+    if (diag) {  // the part kernel skips a diagonal item's h.x and h.m: h.x(a, b) = x.h(b, a), h.m(a, b) = m.h(b, a)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            __syncthreads();  // (tr is read: load_split_item's transpose, the pass before)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = g9[4 + t][r];
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) g9[6 + t][r] = tr[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
+        }
+    }
+    dd_epilogue(sh.info, sh.cst, diag, i, h, g9, ld_wind, n_org, own_lo, own_hi, n_snp, l2dd_acc, ws_acc);
+}
+
+// L2DD of the owned slice (out[k] = SNP own_lo + k): 1 + the sum (the self term, as L2's), NaN where L2 is NaN (SNP
+// not computed, or a non-finite sum) and where rstd <= std_thr (flag bit 1 clear: R is undefined)
+__global__ void __launch_bounds__(256) finalize_dd_kernel(const int* __restrict__ Lw, const double* __restrict__ l2dd_acc,
+                                                          const int* __restrict__ ws_acc,
+                                                          const uint8_t* __restrict__ sflags, int n_snp, int own_lo,
+                                                          int own_hi, double* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, g = own_lo + k;
+    if (g >= own_hi) return;
+    double v = __builtin_nan("");
+    if (Lw[g] >= 0 && (sflags[g] & 2)) {
+        const int nanf = ws_acc[3 * (size_t)n_snp + g];
+        if (!(nanf & (1 | 4))) v = 1.0 + (double)reinterpret_cast<const long long*>(l2dd_acc)[g] / ACC_SCALE;
+    }
+    out[k] = v;
 }
 
 // ---- partitioned LD scores: L2[j, c] = sum_k a[k, c] r2adj(j, k) per annotation column c (and the dominance sum) ----
@@ -4114,6 +4255,26 @@ hipError_t launch_band_f4_cov(const BandArgs& a, const CovArgs& cv, int P, const
     return hipGetLastError();
 }
 
+hipError_t launch_band_f4_dd(const BandArgs& a, int P, const int4* items, int n_items, float* gram, double* l2dd_acc) {
+    if (n_items <= 0) return hipSuccess;
+    if (!a.dom || a.blk_rep != nullptr || l2dd_acc == nullptr) return hipErrorInvalidValue;
+    if (a.n_it > F4_SEG_CHUNKS || P < 1 || 2 * P > a.n_it) return hipErrorInvalidValue;  // (as launch_f4_part)
+    hipLaunchKernelGGL((band_f4_part_kernel<true, true>), dim3((unsigned)n_items * (unsigned)P), dim3(64), 0, a.st,
+                       A_ROWS, a.cst, items, A_SNPS, P, gram, nullptr, a.route_shift);
+    hipLaunchKernelGGL((band_f4_epi_dd_kernel<true>), dim3(n_items), dim3(64), 0, a.st, a.cst, items, A_SNPS, A_EPI, P,
+                       gram, l2dd_acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_finalize_dd(const int* Lw, const double* l2dd_acc, const int* ws_acc, const uint8_t* sflags,
+                              int n_snp, int own_lo, int own_hi, double* out, hipStream_t st) {
+    const int n = own_hi - own_lo;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(finalize_dd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, Lw, l2dd_acc, ws_acc, sflags, n_snp,
+                       own_lo, own_hi, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_band_f4_pairs(const BandArgs& a, const PairsArgs& pa, int P, const int4* items, int n_items,
                                 float* gram, bool emit, bool run_part) {
     if (n_items <= 0) return hipSuccess;
@@ -4234,11 +4395,11 @@ hipError_t launch_finalize_out(const int* Lw, const double* l2_acc, const double
 
 hipError_t launch_issued_products(const int4* items, int n_items, const int4* items2, int n_items2, const int2* rows,
                                  const uint8_t* blk_miss, int nblk, int kind, bool dom, int routed, int route_shift,
-                                 unsigned long long* out, hipStream_t st) {
+                                 unsigned long long* out, hipStream_t st, bool hh) {
     const int n = n_items + (items2 != nullptr ? n_items2 : 0);
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(issued_products_kernel, dim3((n + 255) / 256), dim3(256), 0, st, items, n_items, items2,
-                       n_items2, rows, blk_miss, nblk, kind, dom ? 1 : 0, routed, route_shift, out);
+                       n_items2, rows, blk_miss, nblk, kind, dom ? 1 : 0, routed, route_shift, out, hh ? 1 : 0);
     return hipGetLastError();
 }
 

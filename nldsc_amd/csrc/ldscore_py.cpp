@@ -12,7 +12,8 @@
 // individuals to use, strictly ascending; empty: everyone — nldsc_ld_calculate_keep) and `annot` (an
 // annotation matrix, row-major [n_snp][n_annot]; empty: none — nldsc_ld_calculate_annot), and
 // LDScoreResult two, `l2_annot` and `l2d_annot` (row-major [n_snp][n_annot], empty without `annot`);
-// errors carry the engine's message.
+// LDScoreParams `dom_dom` (dominance-by-dominance LD scores — nldsc_ld_calculate_domdom; not with `annot`) fills
+// LDScoreResult `l2dd` ([n_snp], empty without it); errors carry the engine's message.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -40,6 +41,7 @@ struct LDScoreParams {  // data.h:33-65
     int device = -1;
     std::vector<int> keep;  // .fam lines of the individuals to use (empty: everyone); n_org stays the file's count
     std::vector<double> annot;  // annotation matrix, row-major [n_snp][n_annot] (empty: none)
+    bool dom_dom = false;       // also the dominance-by-dominance scores (LDScoreResult::l2dd)
 
     LDScoreParams() {
         if (const char* d = std::getenv("NLDSC_DEVICE")) device = std::atoi(d);
@@ -62,6 +64,7 @@ struct LDScoreResult {  // data.h:21-31
     std::vector<double> l2, l2d, maf, residuals_std;
     std::vector<int> l2_ws, l2d_ws, l2d_wse;
     std::vector<double> l2_annot, l2d_annot;  // row-major [n_snp][n_annot]; empty without LDScoreParams::annot
+    std::vector<double> l2dd;                 // [n_snp]; empty without LDScoreParams::dom_dom
 };
 
 LDScoreResult calculate(const LDScoreParams& params) {
@@ -92,7 +95,19 @@ LDScoreResult calculate(const LDScoreParams& params) {
                       reinterpret_cast<int32_t*>(res.l2d_wse.data())};
     char err[1024] = {0};
     int rc;
-    if (!params.annot.empty()) {
+    if (params.dom_dom) {
+        if (!params.annot.empty())
+            throw std::invalid_argument(
+                "dom-dom scores with annotations, a pair table or covariates in one run are not supported");
+        std::vector<double> dd(n, 0.0);
+        {
+            py::gil_scoped_release nogil;
+            rc = nldsc_ld_calculate_domdom(&p, params.keep.empty() ? nullptr
+                                                                   : reinterpret_cast<const int32_t*>(params.keep.data()),
+                                           (int32_t)params.keep.size(), &r, dd.data(), err, sizeof(err));
+        }
+        if (rc == NLDSC_OK) res.l2dd = std::move(dd);
+    } else if (!params.annot.empty()) {
         if (n == 0 || params.annot.size() % n != 0)
             throw std::invalid_argument("annot must have n_snp * n_annot elements");
         const size_t C = params.annot.size() / n;
@@ -147,7 +162,8 @@ PYBIND11_MODULE(_ldscore, m) {
         .def_readwrite("flags", &LDScoreParams::flags)
         .def_readwrite("device", &LDScoreParams::device)
         .def_readwrite("keep", &LDScoreParams::keep)
-        .def_readwrite("annot", &LDScoreParams::annot);
+        .def_readwrite("annot", &LDScoreParams::annot)
+        .def_readwrite("dom_dom", &LDScoreParams::dom_dom);
 
     py::class_<LDScoreResult> R(m, "LDScoreResult");
     R.def(py::init());
@@ -159,7 +175,8 @@ PYBIND11_MODULE(_ldscore, m) {
         .def_readwrite("l2d_ws", &LDScoreResult::l2d_ws)
         .def_readwrite("l2d_wse", &LDScoreResult::l2d_wse)
         .def_readwrite("l2_annot", &LDScoreResult::l2_annot)
-        .def_readwrite("l2d_annot", &LDScoreResult::l2d_annot);
+        .def_readwrite("l2d_annot", &LDScoreResult::l2d_annot)
+        .def_readwrite("l2dd", &LDScoreResult::l2dd);
 
     m.def("calculate", &calculate);
     m.attr("__version__") = nldsc_version();

@@ -162,6 +162,26 @@ class Engine:
                                                ctypes.byref(res), err, len(err)), err)
         return arrs
 
+    def run_domdom(self, ld_wind, maf, std_thr, rsq_thr, positions, *, own=None, flags=0, annot=None, covar=None,
+                   pairs=False):
+        """`run` plus the dominance-by-dominance LD scores (C ABI nldsc_engine_run_domdom): the usual dict and
+        "l2dd" (float64 [n_snp]): 1 + the sum of r2adj(R_j . R_k / N) over the pairs l2d_ws[j] counts, NaN where l2
+        is NaN and where SNP j's dominance residual is constant; entries outside the owned range are NaN.  The run
+        takes the closed-form vectors of rare variants (FLAG_EXACT_RARE is implied).  Annotations, covariates and a
+        pair table go in runs of their own."""
+        if annot is not None or covar is not None or pairs:
+            raise _lib.NLDSCError(
+                _lib.E_ARG, "dom-dom scores with annotations, a pair table or covariates in one run are not supported")
+        n = self.n_snp
+        own = (0, n) if own is None else own
+        p, _keep = _lib.make_params(n, self.n_org, ld_wind, maf, std_thr, rsq_thr, positions, flags=flags)
+        arrs, res = _lib.alloc_result(n)
+        arrs["l2dd"] = np.full(n, np.nan)
+        err = _lib.errbuf()
+        _lib.check(self._L.nldsc_engine_run_domdom(self._h, ctypes.byref(p), int(own[0]), int(own[1]),
+                                                   ctypes.byref(res), arrs["l2dd"].ctypes.data, err, len(err)), err)
+        return arrs
+
     def covar_projections(self, n_covar: int) -> dict:
         """The projections of the last covariate run (C ABI nldsc_engine_covar_projections): "u", "w" [n_snp, q]
         (U_j = Q^T A_j in the file's allele coding, W_j = Q^T R_j), "v", "wd" [n_snp] (the shares of the additive /
@@ -297,15 +317,26 @@ class Engine:
 
 
 def calculate(bedfile: str, n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, *, flags=0, device=-1,
-              keep=None, annot=None, covar=None) -> dict:
+              keep=None, annot=None, covar=None, dom_dom=False) -> dict:
     """One-shot C-ABI call `nldsc_ld_calculate` (file -> GPU -> results); with `keep` (0-based .fam line numbers,
     strictly ascending; n_org stays the file's count) `nldsc_ld_calculate_keep`, on those individuals only; with
     `annot` ([n_snp, C]) `nldsc_ld_calculate_annot`, which adds "l2_annot" and "l2d_annot" ([n_snp, C]); with `covar`
-    (an orthonormal basis, one row per individual the run uses) `nldsc_ld_calculate_covar`."""
+    (an orthonormal basis, one row per individual the run uses) `nldsc_ld_calculate_covar`; with `dom_dom`
+    `nldsc_ld_calculate_domdom`, which adds "l2dd" ([n_snp]), not together with `annot` or `covar`."""
     p, _pos = _lib.make_params(n_snp, n_org, ld_wind, maf, std_thr, rsq_thr, positions, bedfile=bedfile,
                                flags=flags, device=device)
     arrs, res = _lib.alloc_result(n_snp)
     err = _lib.errbuf()
+    if dom_dom:
+        if annot is not None or covar is not None:
+            raise _lib.NLDSCError(
+                _lib.E_ARG, "dom-dom scores with annotations, a pair table or covariates in one run are not supported")
+        idx = None if keep is None or len(keep) == 0 else np.ascontiguousarray(keep, dtype=np.int32)
+        arrs["l2dd"] = np.full(n_snp, np.nan)
+        _lib.check(_lib.lib().nldsc_ld_calculate_domdom(
+            ctypes.byref(p), None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx),
+            ctypes.byref(res), arrs["l2dd"].ctypes.data, err, len(err)), err)
+        return arrs
     if covar is not None:
         if annot is not None:
             raise _lib.NLDSCError(_lib.E_ARG, "covariates with annotations or a pair table in one run are not supported")

@@ -20,7 +20,8 @@ from ..core.common import NLDSCParameterError, elapsed_time
 from ..core.logger import log
 from .common import (AnnotFile, FAMFile, BIMFile, LDWindow, MAF, ResidualsSTDThreshold, RSQThreshold,
                      kept_individuals)
-from .routine import (PAIRS_BUDGET, annot_output, covar_basis_of_run, m_annot_values, m_values, make_output,
+from .routine import (PAIRS_BUDGET, annot_output, covar_basis_of_run, domdom_output, m_annot_values, m_values,
+                      make_output, reject_domdom_options,
                       reject_covar_options, reject_pairs_options, reject_sharded_annot, run_pairs_to_file,
                       write_m_annot_file, write_m_file, write_scores)
 
@@ -85,8 +86,10 @@ def _default_runner(device: int, keep=None, n_org_file: int = 0):
         eng.set_keep(keep, n_org_file)
 
     def run(bed_path: str, n_snp: int, n_org: int, ld_wind, maf, std_thr, rsq_thr, positions, flags, annot=None,
-            pairs=None, covar=None):
+            pairs=None, covar=None, dom_dom=False):
         eng.load_bed_file(bed_path, n_snp, n_org)
+        if dom_dom:  # (--dom-dom: the usual arrays plus "l2dd")
+            return eng.run_domdom(ld_wind, maf, std_thr, rsq_thr, positions, flags=flags), eng.timings()
         if covar is not None:  # (--covar: the orthonormal basis, one row per individual of the image)
             return eng.run(ld_wind, maf, std_thr, rsq_thr, positions, flags=flags, covar=covar), eng.timings()
         if pairs is not None:  # (--pairs-out: dict(path, bim, min_r2, budget))
@@ -104,7 +107,7 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
                         progress: bool | None = None, keep: str | None = None,
                         remove: str | None = None, annot: str | None = None, pairs_out: str | None = None,
                         pairs_min_r2: float | None = None, pairs_budget: int = PAIRS_BUDGET,
-                        covar: str | None = None) -> dict:
+                        covar: str | None = None, dom_dom: bool = False) -> dict:
     """Returns {chromosome: output DataFrame (None when written to `out`)} for the chromosomes this rank
     processed.  `keep` / `remove`: `FID IID` lists as in estimate_lds; every chromosome's .fam must resolve to the
     same individuals (a `runner` given by the caller then receives them as the keyword `keep`).  `annot`: an LDSC
@@ -113,7 +116,11 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
     LD table, as in estimate_lds (a runner then receives dict(path, bim, min_r2, budget) as the keyword `pairs` and
     writes the table itself).  `covar`: one PLINK covariate file for every chromosome, as in estimate_lds: the basis is
     built once, for the first chromosome's .fam — with `covar` every chromosome's .fam must list the same individuals
-    in the same order (a runner then receives the [n, q] basis as the keyword `covar`)."""
+    in the same order (a runner then receives the [n, q] basis as the keyword `covar`).  `dom_dom`: the
+    dominance-by-dominance LD scores of every chromosome, as in estimate_lds (a runner then receives the keyword
+    `dom_dom=True` and returns "l2dd" with the usual arrays)."""
+    if dom_dom:
+        reject_domdom_options(annot, pairs_out, covar, flags, sharded_ok=True)
     if covar is not None:
         reject_covar_options(annot, pairs_out, sharded_ok=True)
     if pairs_out is not None:
@@ -156,6 +163,8 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
         meta.append(dict(chrom=chrom, stem=stem, bim=bim, n_org=fam.n_org, pos=pos,
                          work=float(window_work(pos, ld_wind_.data).sum()) * fam.n_org))
     covar_kw = {} if covar is None else {"covar": covar_basis_of_run(covar, fam0, kept)}
+    if dom_dom:
+        covar_kw["dom_dom"] = True
     mine = assign_units([m["work"] for m in meta], world)[rank]
     log.info(f"[rank {rank}/{world}] {len(mine)} of {len(units)} chromosomes: "
              f"{', '.join(meta[u]['chrom'] for u in mine)}")
@@ -204,12 +213,13 @@ def estimate_lds_genome(bfile: str, ld_wind: float, wind_metric: str, maf_thr: f
         ld = _Res(res)
         names = annot_.names if annot_ is not None else None
         if out is None:
-            df = make_output(m["bim"], ld, extra=extra) if names is None else annot_output(m["bim"], ld, names,
+            df = domdom_output(m["bim"], ld, extra=extra) if dom_dom else \
+                make_output(m["bim"], ld, extra=extra) if names is None else annot_output(m["bim"], ld, names,
                                                                                           extra=extra)
         else:
             df = None
             path = out.replace("@", m["chrom"])
-            write_scores(path, m["bim"], ld, extra=extra, annot_names=names)
+            write_scores(path, m["bim"], ld, extra=extra, annot_names=names, dom_dom=dom_dom)
             if write_m:
                 mm, md = m_values(m["bim"], ld)
                 write_m_file(str(Path(path).with_suffix(".M")), mm, md)

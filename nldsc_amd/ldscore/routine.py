@@ -2,7 +2,7 @@
 
 Parses .bed/.bim/.fam, validates parameters, builds `_ldscore.LDScoreParams`, runs
 `_ldscore.calculate` on the GPU, optionally prints the summary, and writes the TSV
-`CHR SNP BP L2 L2D [MAF WSA WSD WSDE RSTD]` (tab-separated, `%.5f`, NaN as empty field)
+`CHR SNP BP L2 L2D [MAF WSA WSD WSDE RSTD] [L2DD]` (tab-separated, `%.5f`, NaN as empty field)
 to `out`.  Additions: `write_m` writes the `M`/`MD` file the h2 reader looks for
 (nldsc/h2/common.py:115-132,142-144) with exactly the values its fallback would compute.
 """
@@ -24,7 +24,7 @@ from .common import (AnnotFile, BIMFile, CovarFile, LDWindow, MAF, PLINKFile, Re
 __all__ = ["estimate_lds", "make_output", "format_scores", "write_scores", "show_summary", "m_values", "write_m_file",
            "annot_output", "m_annot_values", "write_m_annot_file", "reject_sharded_annot", "reject_pairs_options",
            "PAIRS_HEADER", "PAIRS_BUDGET", "open_pairs", "write_pairs", "run_pairs_to_file", "reject_covar_options",
-           "covar_basis_of_run"]
+           "covar_basis_of_run", "reject_domdom_options", "domdom_output"]
 
 
 def show_summary(ld) -> None:
@@ -37,6 +37,8 @@ def show_summary(ld) -> None:
     click.echo(f"\nShort summary:\n"
                f"- Number of additive non-null LD: {data['L2'].count()}\n"
                f"- Number of non-additive non-null LD: {data['L2D'].count()}\n"
+               + (f"- Number of dominance-by-dominance non-null LD: {int(np.isfinite(np.asarray(ld.l2dd)).sum())}\n"
+                  if len(getattr(ld, "l2dd", ())) else "")
                + str(description))
     click.echo("=" * 62)
 
@@ -92,7 +94,18 @@ def format_scores(bim: BIMFile, ld, *, extra: bool = False) -> bytes:
     return head.encode() + b"".join(parts)
 
 
-def write_scores(path: str, bim: BIMFile, ld, *, extra: bool = False, annot_names=None) -> None:
+def domdom_output(bim: BIMFile, ld, *, extra: bool = False) -> pd.DataFrame:
+    """make_output's table, every column in place, then L2DD (ld.l2dd): the dominance-by-dominance LD scores after
+    all existing columns, so the h2 reader's view of the table is the same."""
+    df = make_output(bim, ld, extra=extra)
+    df["L2DD"] = np.asarray(ld.l2dd, dtype=np.float64)
+    return df
+
+
+def write_scores(path: str, bim: BIMFile, ld, *, extra: bool = False, annot_names=None, dom_dom: bool = False) -> None:
+    if dom_dom:  # (never with annot_names: reject_domdom_options)
+        domdom_output(bim, ld, extra=extra).to_csv(path, sep="\t", index=False, float_format="%.5f")
+        return
     if annot_names is not None:  # partitioned scores: the same table with the per-annotation columns appended
         annot_output(bim, ld, annot_names, extra=extra).to_csv(path, sep="\t", index=False, float_format="%.5f")
         return
@@ -159,6 +172,23 @@ def reject_covar_options(annot: str | None, pairs_out: str | None, *, sharded_ok
     if not sharded_ok and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NLDSCParameterError("--covar (covariate-adjusted LD scores) runs a chromosome on one GPU: launch it "
                                   "without torchrun, or with one rank")
+
+
+def reject_domdom_options(annot: str | None, pairs_out: str | None, covar: str | None, flags: int, *,
+                          sharded_ok: bool = False) -> None:
+    """--dom-dom with --annot, --pairs-out or --covar (the engine's message: they are different runs of the engine),
+    with --additive-only (no dominance residuals), or under torchrun with more than one rank on one chromosome (the
+    ranks' tables are gathered without the L2DD column; a whole-genome run gives every rank whole chromosomes and is
+    fine)."""
+    if annot is not None or pairs_out is not None or covar is not None:
+        raise NLDSCParameterError("--dom-dom cannot be combined with --annot, --pairs-out or --covar: dom-dom scores "
+                                  "with annotations, a pair table or covariates in one run are not supported")
+    if int(flags) & lds.FLAG_ADDITIVE_ONLY:
+        raise NLDSCParameterError("--dom-dom cannot be combined with --additive-only: the dominance-by-dominance "
+                                  "scores need the dominance residuals")
+    if not sharded_ok and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NLDSCParameterError("--dom-dom (dominance-by-dominance LD scores) runs a chromosome on one GPU: launch "
+                                  "it without torchrun, or with one rank")
 
 
 def covar_basis_of_run(covar: str, fam, kept) -> np.ndarray:
@@ -318,8 +348,11 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
                  verbose: int = 0, write_m: bool = False, flags: int = 0, device: int | None = None,
                  progress: bool | None = None, keep: str | None = None, remove: str | None = None,
                  annot: str | None = None, pairs_out: str | None = None, pairs_min_r2: float | None = None,
-                 pairs_budget: int = PAIRS_BUDGET, covar: str | None = None):
-    """`covar`: path of a PLINK covariate file (common.CovarFile): covariate-adjusted LD scores (cov-LDSC) on the
+                 pairs_budget: int = PAIRS_BUDGET, covar: str | None = None, dom_dom: bool = False):
+    """`dom_dom`: also the dominance-by-dominance LD scores L2DD_j = 1 + sum_k r2adj(R_j . R_k / N) (d-LDSC): the
+    column L2DD after all other columns of the table; the run takes the closed-form vectors of rare variants, as a
+    `covar` run does; not with `annot`, `pairs_out`, `covar` or the additive-only flag.
+    `covar`: path of a PLINK covariate file (common.CovarFile): covariate-adjusted LD scores (cov-LDSC) on the
     orthonormal basis of its columns for the run's individuals (covar_basis_of_run), in PLINK's sample order.
     `pairs_out`: also write the pairwise LD table behind the scores there (write_pairs; `.gz` compresses), with
     `pairs_min_r2` only the pairs whose R2 or R2D exceeds it, in engine calls of at most `pairs_budget` pairs; the
@@ -328,6 +361,8 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
     .fam lines of the first minus those of the second, in PLINK's sample order (common.kept_individuals).
     `annot`: path of an LDSC `.annot` / `.annot.gz` file (common.AnnotFile): partitioned LD scores, the table gains
     L2_<name> and L2D_<name> columns and `write_m` also writes `<out>.M_annot`."""
+    if dom_dom:
+        reject_domdom_options(annot, pairs_out, covar, flags)
     if covar is not None:
         reject_covar_options(annot, pairs_out)
     if pairs_out is not None:
@@ -360,6 +395,8 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
     if annot_ is not None:
         params.annot = annot_.data.ravel().tolist()
         log.info(f"Annotations: {len(annot_.names)} columns of {annot}")
+    if dom_dom:
+        params.dom_dom = True
     log.info("Running the estimator. It may take a long time.")
     from ..core.progress import Progress
     bar = Progress(bim_.n_snp, "SNPs", enabled=progress)
@@ -393,7 +430,8 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
         show_summary(ld)
     if out:
         log.info("Writing data to disk...")
-        write_scores(out, bim_, ld, extra=extra, annot_names=annot_.names if annot_ is not None else None)
+        write_scores(out, bim_, ld, extra=extra, annot_names=annot_.names if annot_ is not None else None,
+                     dom_dom=dom_dom)
         if write_m:
             m, md = m_values(bim_, ld)
             write_m_file(str(Path(out).with_suffix(".M")), m, md)
@@ -404,4 +442,6 @@ def estimate_lds(bfile: str, ld_wind: float, wind_metric: str, maf_thr: float = 
         return None
     if annot_ is not None:
         return annot_output(bim_, ld, annot_.names, extra=extra)
+    if dom_dom:
+        return domdom_output(bim_, ld, extra=extra)
     return make_output(bim_, ld, extra=extra)
